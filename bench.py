@@ -8,7 +8,7 @@ masked reward with flight-time cost.  One bench "step" = one fu
 the batch (predict + observe + mean/covariance update + reward) including the episode resets that fall on
 that step (episodes are 40 steps long and staggered so every step sees the stationary mix of factor ranks).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
       N > 1 without WORLD_SIZE in the environment: this process starts the N ranks itself (before it touches the
       GPU) as `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` and relays
       rank 0's JSON line
@@ -16,10 +16,15 @@ that step (episodes are 40 steps long and staggered so every step sees the stati
       bench.py --gpus N --steps K --warmup W          (the driver's form: ranks read RANK / LOCAL_RANK / WORLD_SIZE)
 
 Rank 0 prints ONE JSON line.  `value` = envs of all ranks x K / max-over-ranks wall time of the K timed steps
-(inputs resident in HBM).  `roofline` is measured live with HIP events attached to the streaming kernel's
-dispatches; `cpu_baseline` times the plain-C fp64 oracle (oracle/ipp_oracle.c, a port of the reference's NumPy path)
-on the host cores on a bounded sample of the same workload.  At N = 1 the line also carries `extra`: the same
-measurement for the other BASELINE.json configs that fit one GPU (configs[2], the per-GPU share of configs[3], a
+(inputs resident in HBM), `ms_per_step` = that wall time / K.  A plain run does only that: set up, pre-roll (untimed:
+the stationary rank mix, the clocks' ramp), W warm-up steps, ONE timed region of exactly K steps, the line.  --dump-outputs DIR: after the
+timed steps, what the last one computed goes to DIR/<name>.npy (timed_outputs; same arguments, same inputs).
+
+--full adds everything else, as separate legs after the headline: seven timed regions of K steps (`value` = the median
+one), the one-launch schedule (config.sync_schedule), `roofline` (measured live with HIP events attached to the
+streaming kernel's dispatches), `cpu_baseline` (the plain-C fp64 oracle, oracle/ipp_oracle.c, a port of the reference's
+NumPy path, on the host cores on a bounded sample of the same workload) and, at N = 1 on the default workload, `extra`:
+the same measurement for the other BASELINE.json configs that fit one GPU (configs[2], the per-GPU share of configs[3], a
 configs[4] tree-search wave) and for the headline's neighbours (window 12, predict-only).  Synthetic data, device
 Philox noise keyed on the global env id.
 """
@@ -82,14 +87,24 @@ def build_parser():
     ap.add_argument("--step-priority", type=int, default=0,
                     help="A/B: run the steps on a stream of this priority (-1: above the side stream that generates the next episodes' "
                          "ground truths, whose workgroups then only take the slots the step launches leave free)")
-    ap.add_argument("--regions", type=int, default=7,
-                    help="timed regions of --steps steps each (barrier + sync around every one); `value` is the median region")
+    ap.add_argument("--regions", type=int, default=None,
+                    help="timed regions of --steps steps each (barrier + sync around every one); `value` is the median region.  "
+                         "Default: 1 (a plain run times exactly --steps steps), 7 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline as well: seven timed regions, the one-launch schedule (config.sync_schedule), "
+                         "the roofline leg, the CPU baseline and, at N = 1 on the default workload, the `extra` records.  Without it a run "
+                         "sets up, warms up, times the --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64; see timed_outputs)")
     ap.add_argument("--print-args", action="store_true", help="print the workload key used to match PMC summaries, then exit")
     return ap
 
 
 def parse(argv=None):
-    return build_parser().parse_args(argv)
+    args = build_parser().parse_args(argv)
+    if args.regions is None:
+        args.regions = 7 if args.full else 1
+    return args
 
 
 # --------------------------------------------------------------------------------------------- multi-GPU plumbing
@@ -378,13 +393,49 @@ def pmc_traffic(kernel_name, key):
     return None, None
 
 
+# untimed steps before the warm-up: T reach the stationary rank mix; the rest let the device clocks ramp (one 200-step region right
+# behind a T-step pre-roll ran at 0.0747-0.0751 ms per step, the median of seven such regions at 0.0725, one 20000-step region at 0.0727)
+PREROLL_STEPS = 1000
+
+DUMP_STATE_ENVS = 64        # envs whose mean and variance maps go into --dump-outputs (a fixed, seeded sample)
+DUMP_PER_ENV_MAX = 1 << 20  # more envs than this: the per-env arrays are a fixed, seeded sample as well (keeps a dump under 64 MB)
+
+
+def timed_outputs(env, env_lo):
+    """What the last timed step handed its caller, as host arrays (float32 / float64) for --dump-outputs: every env's reward and
+    status and the factor rank of its state after the step (with the resets that fall on it), plus the mean and variance maps of
+    a fixed, seeded sample of envs.  Env ids are global (env_lo + local index)."""
+    env.wait()
+    eng = env.engine
+    B, n = env.num_envs, eng.n_cells
+    out = {"reward": env.reward.float().cpu().numpy(), "status": env.status.cpu().numpy().astype(np.float64),
+           "rank": eng.ranks().cpu().numpy().astype(np.float64)}
+    if B > DUMP_PER_ENV_MAX:
+        ids = np.sort(np.random.RandomState(1).choice(B, DUMP_PER_ENV_MAX, replace=False))
+        out = {k: v[ids] for k, v in out.items()}
+        out["env_ids"] = (ids + env_lo).astype(np.float64)
+    k = min(B, DUMP_STATE_ENVS, max(1, (32 << 20) // (8 * n)))
+    ids = np.sort(np.random.RandomState(0).choice(B, k, replace=False))
+    out["state_env_ids"] = (ids + env_lo).astype(np.float64)
+    out["state_mean"] = np.stack([env.mean(int(e)).cpu().numpy().reshape(-1) for e in ids]).astype(np.float32)
+    out["state_diag"] = np.stack([env.diag(int(e)).cpu().numpy().reshape(-1) for e in ids]).astype(np.float32)
+    return out
+
+
+def write_outputs(outputs, out_dir, rank=0):
+    """DIR/<name>.npy (rank r > 0 of a multi-GPU run: DIR/<name>_rank<r>.npy)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(out_dir, f"{name}{f'_rank{rank}' if rank else ''}.npy"), arr)
+
+
 # --------------------------------------------------------------------------------------------- the measurement
 def run_env_workload(torch, ranks, device, *, grid, envs_local, env_lo, total_envs, episode_steps, state="factor",
                      window_rows=-1, shuffle_prior=False, tile_threads=0, predict_only=False, fused_resets=True,
-                     steps=80, warmup=8, timed=True, regions=1, parts=1):
+                     steps=80, warmup=8, timed=True, regions=1, parts=1, legs=True, capture=False):
     """One workload: build the batched env, pre-roll to the stationary rank mix, W warm-up steps, the timed region
-    (all ranks), then the roofline leg (same steps again with HIP events on the streaming kernel's dispatches).
-    Returns a dict of plain numbers."""
+    (all ranks), then (legs) the one-launch regions and the roofline leg (same steps again with HIP events on the streaming
+    kernel's dispatches).  Returns a dict of plain numbers; capture: rec["outputs"] = timed_outputs() of the last timed step."""
     from ipp_rl_amd import EngineConfig
     from ipp_rl_amd.vec_env import VecIPPEnv, cell_centre_actions
 
@@ -398,12 +449,14 @@ def run_env_workload(torch, ranks, device, *, grid, envs_local, env_lo, total_en
     # the schedule is the job's, not a rank's: a rank whose streams had to share a queue takes every rank to one launch per step
     # (the one-launch legs add timed regions = barriers: a per-rank choice would leave ranks in different collectives)
     use_parts = ranks.all_agree(env.parts > 1 and bool(env._fused_reset) and env.part_queues_distinct)
-    n_total = T + warmup + (2 * regions + 3) * steps
-    # synthetic inputs resident in HBM before the timed region
-    actions = torch.stack([
-        torch.as_tensor(cell_centre_actions(cfg, t, env_lo, env_lo + B, total_envs, ALTITUDES), dtype=torch.float64)
-        for t in range(n_total)
-    ]).to(device)
+    n_pre = max(T, PREROLL_STEPS)
+    n_total = n_pre + warmup + ((2 * regions + 3) if legs else regions) * steps
+    # synthetic inputs resident in HBM before the timed region (one host buffer, one copy)
+    actions_host = np.empty((n_total, B, 3), dtype=np.float64)
+    for t in range(n_total):
+        actions_host[t] = cell_centre_actions(cfg, t, env_lo, env_lo + B, total_envs, ALTITUDES)
+    actions = torch.from_numpy(actions_host).to(device)
+    del actions_host
     env.reset()
     t_idx = 0
 
@@ -445,10 +498,11 @@ def run_env_workload(torch, ranks, device, *, grid, envs_local, env_lo, total_en
     # pre-roll: reach the stationary mix of episode phases (untimed setup, not warmup) -- issued the way the timed regions issue their
     # steps (whole runs of `steps` steps without a join), so that whatever the runtime sets up the first time that many launches are in
     # flight happens here: the first process on a fresh box spent 35 ms of HOST time inside its first timed region otherwise
-    # (1.75 ms per step in a 20-step region; profiles/r06_experiments.txt 15)
+    # (1.75 ms per step in a 20-step region; profiles/r06_experiments.txt 15).  At least PREROLL_STEPS steps: the device clocks ramp
+    # over the first few hundred steps, which the first timed region otherwise pays for
     done = 0
-    while done < T:
-        k = min(max(steps, 1), T - done)
+    while done < n_pre:
+        k = min(max(steps, 1), n_pre - done)
         if predict_only:  # (the states are built by COMMITTED steps; the predict-only calls of the timed regions write nothing)
             for _ in range(k):
                 env.step(actions[t_idx]); t_idx += 1
@@ -469,12 +523,36 @@ def run_env_workload(torch, ranks, device, *, grid, envs_local, env_lo, total_en
     med = lambda xs: sorted(xs)[len(xs) // 2]  # noqa: E731
     issue_per_rank = ranks.gather(1e3 * med([i for i, _ in issue_s]) / steps)
     own_per_rank = ranks.gather(1e3 * med([o for _, o in issue_s]) / steps)  # (without the wait for the other ranks at the closing barrier)
+    outputs = timed_outputs(env, env_lo) if capture else None
     sync_regions = None
-    if use_parts:
+    if use_parts and legs:
         env.wait()
         sync_regions = [timed_region(run_steps_sync, steps, torch.cuda.synchronize, ranks) for _ in range(max(1, regions))]
     bad = int((env.status != 0).sum().item())
     bad_rewards = int((~torch.isfinite(env.reward)).sum().item())
+    rec = {
+        "parts": env.parts if use_parts else 1,
+        "grid": grid, "envs_local": B, "episode_steps": T, "state": state, "predict_only": bool(predict_only),
+        "window_rows": int(eng.info.window_rows), "tile_threads": int(eng.info.tile_threads),
+        "per_rank_s": per_rank, "elapsed_max_s": elapsed_max, "steps": steps, "warmup": warmup,
+        "region_elapsed_max_s": [r[1] for r in timed_regions], "region_issue_s": [i for i, _ in issue_s], "issue_ms_per_rank": issue_per_rank, "own_ms_per_rank": own_per_rank,
+        "queues": getattr(env, "queue_report", None),
+        "split_min_items": int(getattr(eng.info, "patch_split_min_items", 0)),
+        "bad_status": bad, "bad_rewards": bad_rewards,
+        # (patch kernel: three waves per item, two for launches of at least ipp_info.patch_two_wave_min_items items)
+        "workgroup_threads": (64 * (2 if 0 < int(getattr(eng.info, "patch_two_wave_min_items", 0)) <= B // (env.parts if use_parts else 1)
+                                    else int(eng.info.patch_waves))) if (state == "factor" and int(eng.info.patch_layout)) else int(eng.info.tile_threads),
+        "arena_gb": float(eng.info.arena_bytes) / 1e9,
+        "arena_kind": getattr(eng, "arena_kind", None), "arena_chunk_mib": (getattr(eng.arena, "chunk_bytes", 0) >> 20) or None,
+        "outputs": outputs,
+        # (filled by the legs below)
+        "sync_region_elapsed_max_s": None, "sync_elapsed_max_s": None, "mean_rank_after_step": None,
+    }
+    if not legs:
+        env.close()
+        del env, eng, actions
+        torch.cuda.empty_cache()
+        return rec, cfg
 
     # ---- roofline leg: same steps again with HIP events around the streaming kernel (every rank runs it, rank 0 reports)
     eng.profile(True)
@@ -533,29 +611,18 @@ def run_env_workload(torch, ranks, device, *, grid, envs_local, env_lo, total_en
     if busy_ms_per_step:
         kernel_ms = busy_ms_per_step  # per step: every part's launch, overlapped as scheduled
     achieved = bytes_per_launch / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0
-    rec = {
-        "parts": env.parts if use_parts else 1, "single_launch_ms": single_launch_ms, "part_launches": part_launches,
+    rec.update({
+        "single_launch_ms": single_launch_ms, "part_launches": part_launches,
         "part_launch_ms_avg": part_ms_avg,
         "sync_region_elapsed_max_s": [r[1] for r in sync_regions] if sync_regions else None,
         "sync_elapsed_max_s": median_region(sync_regions)[1] if sync_regions else None,
-        "grid": grid, "envs_local": B, "episode_steps": T, "state": state, "predict_only": bool(predict_only),
-        "window_rows": int(eng.info.window_rows), "tile_threads": int(eng.info.tile_threads),
-        "per_rank_s": per_rank, "elapsed_max_s": elapsed_max, "steps": steps, "warmup": warmup,
-        "region_elapsed_max_s": [r[1] for r in timed_regions], "region_issue_s": [i for i, _ in issue_s], "issue_ms_per_rank": issue_per_rank, "own_ms_per_rank": own_per_rank,
-        "queues": getattr(env, "queue_report", None),
-        "split_min_items": int(getattr(eng.info, "patch_split_min_items", 0)),
-        "mean_rank_after_step": mean_rank_after, "bad_status": bad, "bad_rewards": bad_rewards,
+        "mean_rank_after_step": mean_rank_after,
         "kernel": kernel_name, "kernel_ms": kernel_ms, "launches": down_n if kernel_name == "k_downdate" else gain_n,
         "bytes_per_launch": bytes_per_launch, "mask_reread_bytes_per_launch": mask_reread if state == "factor" else 0.0,
         "necessary_bytes_per_launch": needed if (state == "factor" and needed > 0) else None,
-        # (patch kernel: three waves per item, two for launches of at least ipp_info.patch_two_wave_min_items items)
-        "workgroup_threads": (64 * (2 if 0 < int(getattr(eng.info, "patch_two_wave_min_items", 0)) <= B // (env.parts if use_parts else 1)
-                                    else int(eng.info.patch_waves))) if (state == "factor" and int(eng.info.patch_layout)) else int(eng.info.tile_threads),
         "formula_bytes_per_launch": formula_bytes, "achieved_gbs": achieved,
         "other_kernels_ms_avg": {"k_prepare": prep_ms, "k_gain": gain_ms, "k_downdate": down_ms},
-        "arena_gb": float(eng.info.arena_bytes) / 1e9,
-        "arena_kind": getattr(eng, "arena_kind", None), "arena_chunk_mib": (getattr(eng.arena, "chunk_bytes", 0) >> 20) or None,
-    }
+    })
     env.close()
     del env, eng, actions
     torch.cuda.empty_cache()
@@ -834,9 +901,11 @@ def main(argv=None):
                                     episode_steps=T, state=args.state, window_rows=args.window_rows,
                                     shuffle_prior=args.shuffle_prior, tile_threads=args.tile_threads,
                                     predict_only=args.predict_only, fused_resets=args.fused_resets, steps=args.steps,
-                                    warmup=args.warmup, regions=args.regions, parts=args.parts)
+                                    warmup=args.warmup, regions=args.regions, parts=args.parts, legs=args.full,
+                                    capture=args.dump_outputs is not None)
+    if args.dump_outputs is not None:
+        write_outputs(rec["outputs"], args.dump_outputs, rank)
     if rank == 0:
-        traffic, traffic_source = pmc_traffic(rec["kernel"], workload_key(args))
         out = {
             "metric": "env-steps/s (batched) on 50x50 grid" if args.grid == 50 else f"env-steps/s (batched) on {args.grid}x{args.grid} grid",
             "value": aggregate_rate(total_envs, args.steps, rec["elapsed_max_s"]),
@@ -851,7 +920,10 @@ def main(argv=None):
             "dtype": "f32",
             "data": "synthetic",
             "config": _config_block(args, rec, B, T, total_envs, pinning),
-            "roofline": {
+        }
+        if args.full:  # (the roofline leg ran)
+            traffic, traffic_source = pmc_traffic(rec["kernel"], workload_key(args))
+            out["roofline"] = {
                 "bound": "hbm", "achieved": rec["achieved_gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": rec["achieved_gbs"] / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
                 "traffic_definition": "HBM bytes per step (2 x FETCH_SIZE + WRITE_SIZE, KiB) of the whole batch run as one launch (--parts 1 under --pmc)",
@@ -892,16 +964,15 @@ def main(argv=None):
                 "bytes_per_launch_incl_mask_reread": rec["bytes_per_launch"] + rec["mask_reread_bytes_per_launch"],
                 "full_column_formula_bytes_per_launch": rec["formula_bytes_per_launch"],
                 "other_kernels_ms_avg": rec["other_kernels_ms_avg"],
-            },
-        }
-        if not args.no_cpu_baseline and world == 1:  # (rank 0 at N = 1 only: at N > 1 the ranks are pinned to their share of the cores)
+            }
+        if args.full and not args.no_cpu_baseline and world == 1:  # (rank 0 at N = 1 only: at N > 1 the ranks are pinned to their share of the cores)
             try:
                 out["cpu_baseline"] = cpu_baseline(cfg, args)
             except Exception as exc:  # the baseline is a reported extra; never lose the GPU line over it
                 out["cpu_baseline"] = {"value": None, "unit": "env-steps/s", "cores": 0, "kind": "port",
                                        "sample": f"failed: {exc!r}"}
     # ---- the other configs that fit one GPU, same measurement, short runs (N = 1 default line only)
-    default_line = (world == 1 and not args.no_extra and args.grid == 50 and B == 4096 and T == 40 and args.state == "factor"
+    default_line = (args.full and world == 1 and not args.no_extra and args.grid == 50 and B == 4096 and T == 40 and args.state == "factor"
                     and args.window_rows == -1 and not args.predict_only and not args.shuffle_prior and args.tile_threads == 0)
     if default_line:
         extra = []

@@ -188,3 +188,14 @@ def test_rank_core_plan_is_disjoint_and_follows_the_gpus_numa_nodes(tmp_path):
         (d / "vendor").write_text(vendor + "\n"); (d / "class").write_text(cls + "\n"); (d / "numa_node").write_text(f"{node}\n")
     assert bench.gpu_numa_nodes(str(tmp_path)) == [0, 1]
     assert bench._parse_cpulist("0-3,8,10-11\n") == [0, 1, 2, 3, 8, 10, 11]
+
+
+def test_plain_and_full_runs_options():
+    """A plain run times ONE region of exactly --steps steps; --full restores the seven regions and the legs; --regions overrides."""
+    import bench
+
+    a = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert (a.full, a.regions, a.steps, a.warmup, a.dump_outputs) == (False, 1, 20, 5, None)
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert (a.full, a.regions, a.dump_outputs) == (True, 7, "out")
+    assert bench.parse(["--full", "--regions", "3"]).regions == 3 and bench.parse(["--regions", "2"]).regions == 2

@@ -20,7 +20,7 @@ def test_bench_starts_its_own_ranks_and_reports_the_whole_job():
     env = dict(os.environ, IPP_BENCH_SHARE_GPU="1")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--envs", "256", "--steps", "6", "--warmup", "2",
-           "--no-cpu-baseline", "--no-extra"]
+           "--no-cpu-baseline", "--no-extra", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -52,3 +52,47 @@ def test_bench_starts_its_own_ranks_and_reports_the_whole_job():
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["envs_total"] == 384 and d["config"]["envs_per_gpu"] == 192
+
+
+def test_plain_run_times_the_given_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: one timed region of exactly K steps, the headline keys only, and
+    --dump-outputs writes what the last timed step computed -- identical from run to run for the same arguments."""
+    import numpy as np
+
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    lines = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--envs", "256", "--steps", "6", "--warmup", "2",
+               "--dump-outputs", str(tmp_path / run)]
+        out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+        lines.append([ln for ln in out.stdout.splitlines() if ln.startswith("{")])
+    for ls in lines:
+        assert len(ls) == 1
+        d = json.loads(ls[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 6 and d["warmup"] == 2 and d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert "roofline" not in d and "cpu_baseline" not in d and "extra" not in d
+        cfg = d["config"]
+        assert cfg["timed_regions"] == 1 and len(cfg["region_ms_per_step"]) == 1
+        assert abs(d["ms_per_step"] - cfg["region_ms_per_step"][0]) < 1e-9
+        assert abs(d["value"] - 256 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+        assert cfg["items_with_nonzero_status"] == 0 and cfg["non_finite_rewards"] == 0
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(p.name for p in (tmp_path / "b").iterdir())
+    assert names == ["rank.npy", "reward.npy", "state_diag.npy", "state_env_ids.npy", "state_mean.npy", "status.npy"]
+    total = 0
+    for name in names:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+        total += a.nbytes
+    assert total <= 64 << 20
+    reward, status, rank = (np.load(tmp_path / "a" / f"{n}.npy") for n in ("reward", "status", "rank"))
+    assert reward.shape == status.shape == rank.shape == (256,)
+    assert np.isfinite(reward).all() and (status == 0).all() and (rank > 0).any()
+    ids = np.load(tmp_path / "a" / "state_env_ids.npy")
+    mean, diag = np.load(tmp_path / "a" / "state_mean.npy"), np.load(tmp_path / "a" / "state_diag.npy")
+    assert mean.shape == diag.shape == (len(ids), 2500) and len(ids) == 64 and len(set(ids.tolist())) == 64
+    assert np.isfinite(mean).all() and (diag > 0).all()

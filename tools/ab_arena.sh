@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT"; O=gpurun_out/arena; mkdir -p $O
 run() {  # tag, env assignments, bench args
     tag=$1; shift; envs=$1; shift
     for i in 1 2 3; do
-        env $envs timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra "$@" 2>/dev/null | python3 -c "
+        env $envs timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extra "$@" 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -6,7 +6,7 @@ for rep in 1 2; do
     name=${v%%=*}; rest=""; [[ "$v" == *=* ]] && rest=${v#*=}
     lib=""; [ "$name" != "main" ] && lib="IPP_HIP_LIB=$PWD/tools/probes/libipp_$name.so IPP_AB_OLD_LIB=1"
     IFS=',' read -ra kv <<< "$rest"
-    env $lib "${kv[@]}" python bench.py --no-cpu-baseline --no-extra ${BENCH_ARGS} 2>/dev/null | tail -1 | python -c "
+    env $lib "${kv[@]}" python bench.py --full --no-cpu-baseline --no-extra ${BENCH_ARGS} 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']; c=d['config']
 print('$v', 'value %.2f M' % (d['value']/1e6), 'ms/step %.4f' % d['ms_per_step'], 'kernel_ms %.4f' % r['kernel_ms_avg'], 'frac %.3f' % r['frac'], 'alg MB %.1f' % (r['algorithmic_bytes_per_launch']/1e6), 'bad', c['items_with_nonzero_status'], c['non_finite_rewards'])"

@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT"; O=gpurun_out/ab; mkdir -p $O
 PARTS=("$@"); [ ${#PARTS[@]} -eq 0 ] && PARTS=(1 2 4)
 for rep in 1 2; do
   for p in "${PARTS[@]}"; do
-    python bench.py --no-cpu-baseline --no-extra --parts $p ${BENCH_ARGS} 2>/dev/null | tail -1 | python -c "
+    python bench.py --full --no-cpu-baseline --no-extra --parts $p ${BENCH_ARGS} 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']; c=d['config']
 s=c.get('sync_schedule') or {}

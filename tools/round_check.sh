@@ -5,9 +5,9 @@ cd "$GRAFT_REPO_ROOT"; O=gpurun_out/round; rm -rf $O; mkdir -p $O
 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; tail -3 $O/pytest_gpu.log
 # the DRIVER's protocol first (20-step regions): this is the line BENCH_rNN.json records -- keep it as profiles/rNN_bench_line_driver.json
 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.log 2>&1; tail -1 $O/bench_driver.log | cut -c1-300
-python bench.py > $O/bench_default.log 2>&1; tail -1 $O/bench_default.log | cut -c1-300
+python bench.py --full > $O/bench_default.log 2>&1; tail -1 $O/bench_default.log | cut -c1-300
 # region length against the per-step time (fill / drain of the two-group pipeline, the staged blocks inside short regions)
-for k in 10 20 50 200; do python bench.py --no-cpu-baseline --no-extra --steps $k --warmup 5 2>/dev/null | tail -1 | python -c "
+for k in 10 20 50 200; do python bench.py --full --no-cpu-baseline --no-extra --steps $k --warmup 5 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); c=d['config']
 print('steps', d['steps'], 'value %.2f M' % (d['value']/1e6), 'ms/step %.4f' % d['ms_per_step'], 'host issue %.4f' % (c.get('host_issue_ms_per_step') or 0), 'regions', ['%.4f' % x for x in c['region_ms_per_step']])"; done > $O/region_sweep.txt 2>&1; cat $O/region_sweep.txt
@@ -30,10 +30,10 @@ bash tools/ab_arena.sh > /dev/null 2>&1; cp gpurun_out/arena/ab_arena.txt $O/ab_
 grep -v amdgpu.ids $O/extras.txt | tail -12
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 # kernel trace of the headline command line (no extras: one workload per trace)
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o kt -- python3 bench.py --no-cpu-baseline --no-extra > $O/trace.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o kt -- python3 bench.py --full --no-cpu-baseline --no-extra > $O/trace.log 2>&1
 python tools/trace_overlap.py $O/trace/kt_kernel_trace.csv k_step_patch 300 $O/trace.log > $O/trace_overlap.txt 2>&1; grep -v "^  queue" $O/trace_overlap.txt | head -12
 # and of configs[2]
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_cfg2 -o kt -- python3 bench.py --no-cpu-baseline --no-extra --grid 100 --envs 32768 --episode-steps 16 --steps 20 --warmup 4 > $O/trace_cfg2.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_cfg2 -o kt -- python3 bench.py --full --no-cpu-baseline --no-extra --grid 100 --envs 32768 --episode-steps 16 --steps 20 --warmup 4 > $O/trace_cfg2.log 2>&1
 # configs[4]: the tree wave (k_tree_patch) and the device-side search (k_mcts_*)
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_tree -o kt -- python3 tools/tree_wave.py --reps 2 > $O/trace_tree.log 2>&1; tail -1 $O/trace_tree.log | cut -c1-300
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_mcts -o kt -- python3 tools/mcts_bench.py --reps 2 > $O/trace_mcts.log 2>&1; tail -1 $O/trace_mcts.log | cut -c1-300

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define IPP_ABI_VERSION 14
+#define IPP_ABI_VERSION 15
 
 /* covariance state representation */
 #define IPP_DENSE  0 /* P[N][N] fp32 per env, updated in place (mapping/grid_maps.py:10-11)         */
@@ -43,6 +43,13 @@ extern "C" {
 #define IPP_UPDATE_PREV     32u /* after the cost is taken, prev_action[item] <- action[item]: the driver's    */
                                 /* "previous_action = action" (planning/mcts_zero/episode_generators.py:146)  */
                                 /* without a copy kernel; prev_action must then be writable device memory     */
+#define IPP_BUDGET          64u /* per-env budget ledger (ipp_set_budget): remaining_budget -= action cost, depth += 1, done =   */
+                                /* !(depth < max_steps && remaining_budget >= resolution), the episode loop of                */
+                                /* planning/mcts_zero/episode_generators.py:109-150 evaluated after the step                     */
+#define IPP_RESET_ON_DONE  128u /* with IPP_BUDGET: a done env resets in the same launch (alternate-plane flip), its ledger     */
+                                /* restarts and refill[position] names it for ipp_generate_grf_refill                           */
+#define IPP_BUDGET_STREAM (3ull << 40) /* Philox subsequence base of the shuffled start budgets: episode j of global env g draws  */
+                                       /* its budget from subsequence IPP_BUDGET_STREAM + j, counter g                          */
 
 /* per-item status written by ipp_step */
 #define IPP_STATUS_OK            0
@@ -234,6 +241,27 @@ int ipp_step_parts(void* engine, int32_t n, const double* action, double* prev_a
 int ipp_set_reset_prior(void* engine, const double* prior);
 
 /*
+ * Budget ledger of the batched driver (IPP_BUDGET / IPP_RESET_ON_DONE steps of ipp_step_autoreset and ipp_step_parts; full-batch
+ * in-place steps, env_ids == NULL, of patch-layout engines: ipp_info.patch_layout == 1).  Replaces the per-episode bookkeeping of the
+ * self-play loop, planning/mcts_zero/episode_generators.py:109-150: remaining_budget = sample_budget() (:113, initial_budget, or
+ * int(U(10, initial_budget)) with shuffle_budget), `while depth < max_episode_steps and remaining_budget >= grid_map.resolution`,
+ * remaining_budget -= action_costs(action, previous_action, uav_specifications) (planning/common/actions.py:8-41), depth += 1.
+ * The caller owns the arrays and installs them once; the pointers are kept, not copied (NULL budget: uninstall).
+ *   budget  [dev] double[capacity]  remaining budget of every env's current episode (charged with the step's cost, whatever its status)
+ *   depth   [dev] int32[capacity]   steps taken in the current episode
+ *   episode [dev] int64[capacity]   0-based index of the env's current episode (advanced by a reset on done)
+ *   done    [dev] uint8[n]          per item of the last step: the loop condition above is false after it (a NaN cost ends the episode)
+ *   refill  [dev] int32[n]          per DISPATCH POSITION of the last IPP_RESET_ON_DONE step: the env that reset there, else -1
+ *   initial_budget, shuffle_budget  start budget of an episode: initial_budget, or floor(10 + u (initial_budget - 10)) with u the
+ *                                   Philox uniform of counter (env + row_offset), subsequence IPP_BUDGET_STREAM + episode, key seed
+ *   max_steps                       max_episode_steps
+ * A reset on done is ipp_step_autoreset's flip to the alternate ground-truth plane (reset_gt == NULL): mean 0.5, the config's prior,
+ * rank 0, prev_action[env] <- init_action; ipp_generate_grf_refill stages the next field behind every such step.
+ */
+int ipp_set_budget(void* engine, double* budget, int32_t* depth, int64_t* episode, uint8_t* done, int32_t* refill,
+                   double initial_budget, int32_t max_steps, int32_t shuffle_budget, uint64_t seed, int64_t row_offset);
+
+/*
  * Reward of n candidate actions from the CURRENT state of ONE env slot; nothing is written.  The call of
  * greedy_search and of the rollout policy: simulate_prediction_step for every reachable action from the same
  * state (planning/common/optimization.py:33-104, planning/mcts_mission.py:232-246).
@@ -410,6 +438,14 @@ int ipp_generate_grf_rows(void* engine, int32_t n, const int32_t* row_ids, int64
 int ipp_generate_grf_groups(void* engine, int32_t n, int32_t group_rows, const int64_t* group_subsequence /*[host] or NULL*/,
                             const int32_t* row_ids /*[dev] or NULL*/, int64_t row_offset, uint64_t seed, uint64_t subsequence,
                             float* gt_out /*[dev]*/, void* stream);
+/* ... for the resets a budget step decided on the device (IPP_RESET_ON_DONE): field i is written into the ALTERNATE plane of env
+ * refill[i] (a negative entry skips the field) and sets its staged flag; its noise is drawn from subsequence + episode[env] + 1 --
+ * the field of the episode after the one that env has just started, so that a one-step episode finds its next field staged.  Launch
+ * it behind the step on the step's stream, over the n positions of the launch (or over one part's position range on that part's
+ * stream).  Same grids as ipp_generate_grf_rows (-3 elsewhere).  simulations/ground_truths.py:14-33 (the field),
+ * planning/mcts_zero/episode_generators.py:109-113 (a new episode's map, sampled when the previous one has run out of budget). */
+int ipp_generate_grf_refill(void* engine, int32_t n, const int32_t* refill /*[dev]*/, const int64_t* episode /*[dev] int64[capacity]*/,
+                            int64_t row_offset, uint64_t seed, uint64_t subsequence, void* stream);
 
 /*
  * One fused environment step for `n` items.  Replaces, per item:

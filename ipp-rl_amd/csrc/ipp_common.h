@@ -182,6 +182,20 @@ struct View {
 __device__ __forceinline__ float* gt_plane(const View& v, int env) { return v.gt + (size_t)v.gt_slot[env] * v.Npad; }
 __device__ __forceinline__ int gt_alt_slot(const View& v, int env) { const int s = v.gt_slot[env]; return s >= v.cap ? s - v.cap : s + v.cap; }
 
+// Budget ledger of the batched driver (ipp_set_budget; read only by the IPP_BUDGET instantiations of the patch step): the episode
+// loop of planning/mcts_zero/episode_generators.py:109-150 per env.
+struct Ledger {
+    double* budget;     // [capacity] remaining budget of the current episode
+    int* depth;         // [capacity] steps taken in it
+    long long* episode; // [capacity] 0-based index of the current episode
+    unsigned char* done; // [n] per item of the last step
+    int* refill;        // [n] per dispatch position of the last IPP_RESET_ON_DONE step: the env that reset there, else -1
+    double b0, res;     // initial_budget, grid resolution (the loop's threshold)
+    int max_steps, shuffle;
+    uint64_t seed;
+    long long row_offset;
+};
+
 // Episode reset folded into a step launch (ipp_step_autoreset): item i resets its env after its step when
 // src[i] >= 0, taking ground truth gt[src[i]] ([N] floats).  Mission.init_action by value.
 struct AutoReset {
@@ -190,7 +204,23 @@ struct AutoReset {
     const double* prior; // [..][2] prior (sigma^2, l) of the new episode that takes ground truth k, or NULL: the config's (ipp_set_reset_prior)
     double* prev;       // [capacity][3] indexed by env id, or NULL
     double init[3];
+    Ledger led;         // IPP_BUDGET launches only (the other instantiations never read it)
 };
+
+__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t (&k)[2]);  // (k_misc.h)
+
+// Start budget of episode `episode` of env `env` (sample_budget, episode_generators.py:113 with shuffle_budget:
+// int(U(10, initial_budget))): floor(10 + u (b0 - 10)), u the Philox4x32-10 uniform of counter (env + row_offset),
+// subsequence IPP_BUDGET_STREAM + episode, key seed -- keyed on the global env id like the ground truths.
+__device__ __forceinline__ double budget_start(const Ledger& L, int env, long long episode) {
+    if (!L.shuffle) return L.b0;
+    const uint64_t q = (uint64_t)((long long)env + L.row_offset), sub = (uint64_t)IPP_BUDGET_STREAM + (uint64_t)episode;
+    uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32), (uint32_t)sub, (uint32_t)(sub >> 32)};
+    uint32_t k[2] = {(uint32_t)L.seed, (uint32_t)(L.seed >> 32)};
+    for (int r = 0; r < 10; ++r) philox_round(c, k);
+    const double u = ((double)c[0] + 0.5) * (1.0 / 4294967296.0);
+    return floor(__dadd_rn(10.0, __dmul_rn(u, L.b0 - 10.0)));  // (rounded product, then the sum: no contraction, the host's NumPy value)
+}
 
 // One wave resets env `env` (mapping/mappings.py:235-240,259-261: mean 0.5, P = prior; factor state: rank 0) and
 // installs ground truth field k.  The caller guarantees that every earlier store / atomic to the env's planes

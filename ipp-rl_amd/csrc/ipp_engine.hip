@@ -114,6 +114,7 @@ struct Engine {
     int pcap2 = 0, two_wave_min_items = 0;
     size_t lds2 = 0;
     const double* reset_prior = nullptr;  // ipp_set_reset_prior: priors of the episodes started by ipp_step_autoreset
+    Ledger led = {};                      // ipp_set_budget: the budget ledger of IPP_BUDGET steps (budget == NULL: none installed)
     bool rect_ok = false;      // rectangle tiles (k_gain_factor.h) possible: clipped windows, 128-cell tiles, even grid width
     bool rect_commit = false;  // ... used for committed steps too (else for predict-only calls only)
     bool rect_tree = false;    // tree steps on rectangle tiles (same width rule; either tile size)
@@ -458,7 +459,27 @@ void launch_chunk(Engine* e, const View& v, const int32_t* env_ids, const int32_
                   hipEvent_t prep_done, const AutoReset& ar) {
     if (e->patch) {  // compact column patches: one fused kernel, one small workgroup per item (k_step_patch.h)
         if constexpr (MC == 9 && VEC == 2) {
-            if (e->split_min_items > 0 && n >= e->split_min_items) {
+            if (flags & IPP_BUDGET) {
+                // the budget ledger: the IPP_BUDGET instantiations of the fused kernels the launch would run otherwise (budget_launch_error
+                // has refused the split step and the one- / four-wave A/B engines)
+                if (e->patch_waves == 3 && !(e->two_wave_min_items > 0 && n >= e->two_wave_min_items)) {
+                    if (v.rank_cap <= 192)
+                        timed_launch(e, 0, k_step_patch<3, kPatchKP, kPatchMinW, false, 1, true>, dim3(n), dim3(192), e->gain_lds, s, v, env_ids, n, action, prev, noise, flags, status, reward, ar);
+                    else if (v.rank_cap <= 384)
+                        timed_launch(e, 0, k_step_patch<3, kPatchKP, kPatchMinW, false, 2, true>, dim3(n), dim3(192), e->gain_lds, s, v, env_ids, n, action, prev, noise, flags, status, reward, ar);
+                    else
+                        timed_launch(e, 0, k_step_patch<3, kPatchKP, kPatchMinW, false, 0, true>, dim3(n), dim3(192), e->gain_lds, s, v, env_ids, n, action, prev, noise, flags, status, reward, ar);
+                } else if (e->big_min_items > 0 && n >= e->big_min_items) {
+                    View vb = v;
+                    vb.pcap = e->pcap_big;
+                    timed_launch(e, 0, k_step_patch<2, IPP_PATCH_BIGKP, 6, false, 0, true>, dim3(n), dim3(128), e->lds_big, s, vb, env_ids, n, action, prev, noise, flags, status, reward, ar);
+                } else {
+                    View v2 = v;
+                    if (e->patch_waves == 3) v2.pcap = e->pcap2;
+                    timed_launch(e, 0, k_step_patch<2, kPatchKP, kPatchMinW, false, 0, true>, dim3(n), dim3(128), e->patch_waves == 3 ? e->lds2 : e->gain_lds, s, v2, env_ids,
+                                 n, action, prev, noise, flags, status, reward, ar);
+                }
+            } else if (e->split_min_items > 0 && n >= e->split_min_items) {
                 // split step (k_step_split.h): item-parallel prologue kernel, then one wave per (item, unit)
                 View vp = v;
                 vp.pcap = e->pcap_p;
@@ -673,7 +694,10 @@ int launch_grf(Engine* e, int n, const float* white, float* raw, const int32_t* 
         const int np = 16 * e->grf_tt;
         const double* ampt = (const double*)v.grf_amp;
         const double2* twt = (const double2*)v.grf_cs;
-        if (v.W == 100) hipLaunchKernelGGL((k_grf_fft<10, float>), dim3(n), dim3(512), grf_fft_lds_bytes(100, 4), s, v, env_ids, n, white, ampt, np, gt_out, gn, twt);
+        if (gn.episode) {  // ipp_generate_grf_refill
+            if (v.W == 100) hipLaunchKernelGGL((k_grf_fft<10, float, true>), dim3(n), dim3(512), grf_fft_lds_bytes(100, 4), s, v, env_ids, n, white, ampt, np, gt_out, gn, twt);
+            else hipLaunchKernelGGL((k_grf_fft<5, float, true>), dim3(n), dim3(256), grf_fft_lds_bytes(50, 4), s, v, env_ids, n, white, ampt, np, gt_out, gn, twt);
+        } else if (v.W == 100) hipLaunchKernelGGL((k_grf_fft<10, float>), dim3(n), dim3(512), grf_fft_lds_bytes(100, 4), s, v, env_ids, n, white, ampt, np, gt_out, gn, twt);
         else hipLaunchKernelGGL((k_grf_fft<5, float>), dim3(n), dim3(256), grf_fft_lds_bytes(50, 4), s, v, env_ids, n, white, ampt, np, gt_out, gn, twt);
         HIP_TRY(hipGetLastError());
         return 0;
@@ -1167,7 +1191,7 @@ static int step_impl(void* engine, const int32_t* env_ids, const int32_t* dst_id
     if (n < 0 || n > e->v.max_batch) return fail(-1, "n = %d outside [0, max_batch = %d]", n, e->v.max_batch);
     if (n == 0) return 0;
     if (!env_ids && n > e->v.cap) return fail(-1, "n exceeds capacity");
-    if (flags & ~(IPP_COV_ONLY | IPP_PREDICT_ONLY | IPP_ADAPTIVE | IPP_USE_FLIGHT_TIME | IPP_GIVEN_OBSERVATION | IPP_UPDATE_PREV)) return fail(-1, "unknown flag bits 0x%x", flags);
+    if (flags & ~(IPP_COV_ONLY | IPP_PREDICT_ONLY | IPP_ADAPTIVE | IPP_USE_FLIGHT_TIME | IPP_GIVEN_OBSERVATION | IPP_UPDATE_PREV | IPP_BUDGET | IPP_RESET_ON_DONE)) return fail(-1, "unknown flag bits 0x%x", flags);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     HIP_TRY(hipSetDevice(e->device));
     e->last_n = n;
@@ -1198,8 +1222,49 @@ static int step_impl(void* engine, const int32_t* env_ids, const int32_t* dst_id
 int ipp_step(void* engine, const int32_t* env_ids, const int32_t* dst_ids, int32_t n, const double* action,
              const double* prev_action, const float* meas_noise, uint32_t flags, float* reward, int32_t* status,
              void* stream) {
+    if (flags & (IPP_BUDGET | IPP_RESET_ON_DONE)) return fail(-1, "ipp_step: IPP_BUDGET / IPP_RESET_ON_DONE are flags of ipp_step_autoreset and ipp_step_parts");
     const AutoReset none = {nullptr, nullptr, nullptr, nullptr, {0.0, 0.0, 0.0}};
     return step_impl(engine, env_ids, dst_ids, n, action, prev_action, meas_noise, flags, reward, status, stream, none);
+}
+
+// Why a budget step (IPP_BUDGET / IPP_RESET_ON_DONE) cannot run on this engine with these arguments, or nullptr.  The ledger lives in
+// the fused patch-step kernels only: no silent fallback to a path without it.  n: items of one launch (a part's, for ipp_step_parts).
+static const char* budget_launch_error(const Engine* e, uint32_t flags, int n, const int32_t* env_ids, const int32_t* reset_src,
+                                       const float* reset_gt, const double* init_action) {
+    if (!(flags & (IPP_BUDGET | IPP_RESET_ON_DONE))) return nullptr;
+    if (!(flags & IPP_BUDGET)) return "IPP_RESET_ON_DONE needs IPP_BUDGET";
+    if (!e->led.budget) return "IPP_BUDGET: no ledger installed (ipp_set_budget)";
+    if (e->v.mode != IPP_FACTOR || !e->patch || !e->fused) return "IPP_BUDGET: patch-layout factor engines only (ipp_info.patch_layout == 1)";
+    if (flags & IPP_PREDICT_ONLY) return "IPP_BUDGET: not with IPP_PREDICT_ONLY (the ledger charges committed steps)";
+    if (env_ids) return "IPP_BUDGET: full-batch in-place steps only (env_ids == NULL)";
+    if (n > e->v.cap) return "IPP_BUDGET: more items than env slots";
+    if (e->split_min_items > 0 && n >= e->split_min_items) return "IPP_BUDGET: not on the split step (IPP_SPLIT)";
+    if (e->patch_waves != 2 && e->patch_waves != 3) return "IPP_BUDGET: engines of two or three waves per item only (IPP_PATCH_WAVES)";
+    if (e->step_chunks > 1) return "IPP_BUDGET: not with a chunked step (IPP_STEP_CHUNKS)";
+    if (flags & IPP_RESET_ON_DONE) {
+        if (reset_src || reset_gt) return "IPP_RESET_ON_DONE: the resets come from the ledger (reset_src and reset_gt must be NULL)";
+        if (!init_action) return "IPP_RESET_ON_DONE needs init_action";
+        if (e->reset_prior) return "IPP_RESET_ON_DONE: no per-episode reset priors (ipp_set_reset_prior)";
+    }
+    return nullptr;
+}
+
+int ipp_set_budget(void* engine, double* budget, int32_t* depth, int64_t* episode, uint8_t* done, int32_t* refill,
+                   double initial_budget, int32_t max_steps, int32_t shuffle_budget, uint64_t seed, int64_t row_offset) {
+    Engine* e = as_engine(engine);
+    if (!e) return fail(-1, "null engine");
+    if (!budget) { e->led = Ledger{}; return 0; }
+    if (!depth || !episode || !done || !refill) return fail(-1, "ipp_set_budget: budget, depth, episode, done and refill are required");
+    if (!e->patch) return fail(-1, "ipp_set_budget: patch-layout factor engines only (ipp_info.patch_layout == 1)");
+    if (!(initial_budget >= e->v.res)) return fail(-1, "ipp_set_budget: initial_budget %g below the resolution %g", initial_budget, e->v.res);
+    if (shuffle_budget && !(initial_budget >= 10.0)) return fail(-1, "ipp_set_budget: shuffle_budget needs initial_budget >= 10");
+    if (max_steps < 1) return fail(-1, "ipp_set_budget: max_steps < 1");
+    Ledger L = {};
+    L.budget = budget; L.depth = depth; L.episode = reinterpret_cast<long long*>(episode); L.done = done; L.refill = refill;
+    L.b0 = initial_budget; L.res = e->v.res; L.max_steps = max_steps; L.shuffle = shuffle_budget ? 1 : 0; L.seed = seed;
+    L.row_offset = (long long)row_offset;
+    e->led = L;
+    return 0;
 }
 
 int ipp_step_autoreset(void* engine, const int32_t* env_ids, int32_t n, const double* action, double* prev_action,
@@ -1210,8 +1275,13 @@ int ipp_step_autoreset(void* engine, const int32_t* env_ids, int32_t n, const do
     if (e->v.mode != IPP_FACTOR) return fail(-1, "ipp_step_autoreset: factor state only (dense engines: ipp_step + ipp_reset_episode)");
     if (flags & IPP_PREDICT_ONLY) return fail(-1, "ipp_step_autoreset: not with IPP_PREDICT_ONLY");
     if (reset_src && !init_action) return fail(-1, "reset_src needs init_action");  // (reset_gt == NULL: the ground truths were staged into the alternate planes)
+    if (const char* why = budget_launch_error(e, flags, n, env_ids, reset_src, reset_gt, init_action)) return fail(-1, "ipp_step_autoreset: %s", why);
     AutoReset ar = {reset_src, reset_gt, reset_src ? e->reset_prior : nullptr, reset_src ? prev_action : nullptr, {0.0, 0.0, 0.0}};
     if (init_action) for (int k = 0; k < 3; ++k) ar.init[k] = init_action[k];
+    if (flags & IPP_BUDGET) {
+        ar.led = e->led;
+        if (flags & IPP_RESET_ON_DONE) ar.prev = prev_action;
+    }
     return step_impl(engine, env_ids, nullptr, n, action, prev_action, meas_noise, flags, reward, status, stream, ar);
 }
 
@@ -1225,7 +1295,7 @@ int ipp_step_parts(void* engine, int32_t n, const double* action, double* prev_a
         return fail(-1, "ipp_step_parts: engines whose step is one fused kernel only (ipp_info.fused_step)");
     // (predict-only parts: reward / status of every item, no state write -- consecutive calls do not depend on each other at all)
     if ((flags & IPP_PREDICT_ONLY) && (reset_src || (flags & IPP_UPDATE_PREV))) return fail(-1, "ipp_step_parts: IPP_PREDICT_ONLY with resets or IPP_UPDATE_PREV");
-    if (flags & ~(IPP_COV_ONLY | IPP_PREDICT_ONLY | IPP_ADAPTIVE | IPP_USE_FLIGHT_TIME | IPP_GIVEN_OBSERVATION | IPP_UPDATE_PREV)) return fail(-1, "unknown flag bits 0x%x", flags);
+    if (flags & ~(IPP_COV_ONLY | IPP_PREDICT_ONLY | IPP_ADAPTIVE | IPP_USE_FLIGHT_TIME | IPP_GIVEN_OBSERVATION | IPP_UPDATE_PREV | IPP_BUDGET | IPP_RESET_ON_DONE)) return fail(-1, "unknown flag bits 0x%x", flags);
     if (n <= 0 || n > e->v.max_batch || n > e->v.cap) return fail(-1, "n = %d outside [1, min(max_batch, capacity)]", n);
     if (!e->v.item_order || e->v.item_order_n != n) return fail(-1, "ipp_step_parts: needs the dispatch order of all n items (ipp_set_item_order)");
     if (n_parts < 1 || n_parts > kMaxChunks) return fail(-1, "n_parts = %d outside [1, %d]", n_parts, kMaxChunks);
@@ -1233,8 +1303,15 @@ int ipp_step_parts(void* engine, int32_t n, const double* action, double* prev_a
     for (int p = 0; p < n_parts; ++p)
         if (part_begin[p + 1] <= part_begin[p]) return fail(-1, "part %d is empty", p);
     if (reset_src && !init_action) return fail(-1, "reset_src needs init_action");
+    for (int p = 0; p < n_parts; ++p)
+        if (const char* why = budget_launch_error(e, flags, part_begin[p + 1] - part_begin[p], nullptr, reset_src, reset_gt, init_action))
+            return fail(-1, "ipp_step_parts: %s", why);
     AutoReset ar = {reset_src, reset_gt, reset_src ? e->reset_prior : nullptr, reset_src ? prev_action : nullptr, {0.0, 0.0, 0.0}};
     if (init_action) for (int k = 0; k < 3; ++k) ar.init[k] = init_action[k];
+    if (flags & IPP_BUDGET) {
+        ar.led = e->led;
+        if (flags & IPP_RESET_ON_DONE) ar.prev = prev_action;
+    }
     HIP_TRY(hipSetDevice(e->device));
     e->last_n = n;
     for (int p = 0; p < n_parts; ++p) {
@@ -1277,6 +1354,19 @@ int ipp_generate_grf_groups(void* engine, int32_t n, int32_t group_rows, const i
     GrfNoise gn = {row_ids, (long long)row_offset, seed, subsequence, group_rows, {0}, gt_out ? 0 : 1};
     for (int g = 0; group_rows > 0 && g < (n + group_rows - 1) / group_rows; ++g) gn.group_subseq[g] = (long long)group_subsequence[g];
     return launch_grf(e, n, nullptr, e->v.grf_raw2, nullptr, gt_out, reinterpret_cast<hipStream_t>(stream), &gn);
+}
+
+int ipp_generate_grf_refill(void* engine, int32_t n, const int32_t* refill, const int64_t* episode, int64_t row_offset, uint64_t seed,
+                            uint64_t subsequence, void* stream) {
+    Engine* e = as_engine(engine);
+    if (!e) return fail(-1, "null engine");
+    if (!refill || !episode) return fail(-1, "ipp_generate_grf_refill: refill and episode are required");
+    if (n < 0 || n > e->v.max_batch) return fail(-1, "n = %d outside [0, max_batch = %d]", n, e->v.max_batch);
+    if (n == 0) return 0;
+    if (!(e->grf_tt > 0 && e->grf_fft)) return fail(-3, "ipp_generate_grf_refill: this grid has no generator that draws its own noise (50x50 / 100x100 grids)");
+    HIP_TRY(hipSetDevice(e->device));
+    GrfNoise gn = {refill, (long long)row_offset, seed, subsequence, 0, {0}, 1, reinterpret_cast<const long long*>(episode)};
+    return launch_grf(e, n, nullptr, e->v.grf_raw2, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream), &gn);
 }
 
 int ipp_observe(void* engine, const int32_t* env_ids, int32_t n, const double* action, const float* meas_noise,

@@ -138,6 +138,7 @@ struct GrfNoise {
     int group_rows;
     long long group_subseq[16];
     int to_alt;  // gt_out == NULL: field i goes to the ALTERNATE ground-truth plane of env row_ids[i] (staged for its next episode; the reset flips)
+    const long long* episode;  // REFILL (ipp_generate_grf_refill): [capacity] current episode of every env; field i draws from subseq + episode[env] + 1
 };
 
 // One workgroup per field.  white [n_items][N] float standard normals (or nullptr: GrfNoise); amp [n][amp_ld] doubles (the table of
@@ -145,7 +146,9 @@ struct GrfNoise {
 // T = float (default): the transforms in fp32 -- inputs and output are fp32 anyway and the field is min-max normalised: 6e-7 of the
 // normalised field against numpy's fp64 path (bar 1e-5, tests/test_hip_big_grids.py), half the LDS (four 100x100 fields per CU) and
 // plain-rate arithmetic (T = double -- the reference's precision end to end -- measured no closer to the bar and is not instantiated).
-template <int N1, typename T>
+// REFILL: the fields of the resets a budget step decided on the device (row_ids = its refill list, to_alt): subsequence per field from
+// the env's episode counter instead of the host's group offsets.
+template <int N1, typename T, bool REFILL = false>
 __global__ __launch_bounds__(N1 == 10 ? 512 : 256) void k_grf_fft(View v, const int* __restrict__ env_ids, int n_items, const float* __restrict__ white,
                                                                   const double* __restrict__ amp, int amp_ld, float* __restrict__ gt_out, GrfNoise gn,
                                                                   const double2* __restrict__ tw) {
@@ -173,7 +176,8 @@ __global__ __launch_bounds__(N1 == 10 ? 512 : 256) void k_grf_fft(View v, const 
             }
         } else {
             const uint64_t rid = (uint64_t)((gn.row_ids ? (long long)gn.row_ids[item] : (long long)item) + gn.row_offset);
-            const uint64_t subseq = gn.subseq + (gn.group_rows > 0 ? (uint64_t)gn.group_subseq[min(item / gn.group_rows, 15)] : 0ull);
+            const uint64_t subseq = REFILL ? gn.subseq + (uint64_t)(gn.episode[env] + 1)
+                                           : gn.subseq + (gn.group_rows > 0 ? (uint64_t)gn.group_subseq[min(item / gn.group_rows, 15)] : 0ull);
             constexpr int qpr = (N + 3) / 4;  // counters per row: element e of the row is normal e & 3 of counter rid * qpr + (e >> 2)
             for (int qc = tid; qc < qpr; qc += NT) {
                 float nrm[4];

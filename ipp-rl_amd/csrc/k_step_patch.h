@@ -170,6 +170,38 @@ struct StepIo {
     }
 };
 
+// IPP_BUDGET: the reference's episode loop condition (planning/mcts_zero/episode_generators.py:109), negated, after the step has been
+// charged: remaining_budget -= cost, depth += 1 (a NaN cost ends the episode).  Item-uniform: every wave evaluates it from the budget and
+// depth it loaded with the inputs and the header's cost.
+__device__ __forceinline__ bool ledger_done(const Ledger& L, double bud, int dep, double cost) {
+    return !(dep + 1 < L.max_steps && bud - cost >= L.res);
+}
+
+// ... and the item's last wave closes the ledger: the charged budget and depth, or -- done with IPP_RESET_ON_DONE -- the reset (the flip to
+// the staged plane), the next episode's start budget, depth 0, the episode counter advanced, and the env's id at the item's dispatch
+// position of refill (each item owns its position: no atomics).  The caller guarantees, as for wave_reset_env, that every earlier store
+// of the item to the env's planes has completed.
+__device__ __forceinline__ void ledger_close(const View& v, const AutoReset& ar, unsigned flags, int env, int item, int pos, double bud,
+                                             int dep, double cost, int lane) {
+    const Ledger& L = ar.led;
+    const bool done = ledger_done(L, bud, dep, cost);
+    const bool rs = done && (flags & IPP_RESET_ON_DONE);
+    if (rs) wave_reset_env(v, ar, env, 0, lane);  // (reset_gt == NULL, no reset prior: k is not read)
+    if (lane == 0) {
+        L.done[item] = done ? 1 : 0;
+        if (rs) {
+            const long long ep = L.episode[env] + 1;
+            L.episode[env] = ep;
+            L.budget[env] = budget_start(L, env, ep);
+            L.depth[env] = 0;
+        } else {
+            L.budget[env] = bud - cost;
+            L.depth[env] = dep + 1;
+        }
+        if (flags & IPP_RESET_ON_DONE) L.refill[pos] = rs ? env : -1;
+    }
+}
+
 template <bool ONE>
 __device__ __forceinline__ void patch_sync() {
     if (ONE) wave_lds_sync(); else __syncthreads();
@@ -180,7 +212,9 @@ __device__ __forceinline__ void patch_sync() {
 // RJN: rounds of NW x 64 threads over the columns' rectangles (tests, compaction); 0 = enough for kPatchMaxRank.  An engine whose rank_cap
 // fits fewer rounds runs the instantiation without the empty ones (configs[2]: 1 of 3, the headline: 2 of 3 -- they are predicated
 // instructions otherwise, 2-3 % of an item's at configs[2], whose step is bound by the vector units).
-template <int NW, int KPN = kPatchKP, int MINW = kPatchMinW, bool SPLIT = false, int RJN = 0>
+// BUD: the IPP_BUDGET form (fused step only, full-batch in-place launches): the ledger of ar.led is charged and closed per item, and with
+// IPP_RESET_ON_DONE the envs it ends are reset in the launch (ledger_close).  The other instantiations do not contain a line of it.
+template <int NW, int KPN = kPatchKP, int MINW = kPatchMinW, bool SPLIT = false, int RJN = 0, bool BUD = false>
 __global__ __launch_bounds__(64 * NW, MINW) void k_step_patch(
     View v, const int* __restrict__ env_ids, int n_items, const double* __restrict__ action,
     const double* __restrict__ prev_action, const float* __restrict__ meas_noise, unsigned flags,
@@ -215,6 +249,10 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_step_patch(
     const double sv_d = v.prior[2 * envc + 0], ls_d = v.prior[2 * envc + 1];
     const int otid = tid - kWave * OW;
     const float eps_ld = (meas_noise && otid >= 0 && otid < MC) ? meas_noise[(size_t)item * MC + otid] : 0.f;
+    double bud_ld = 0.0;
+    int dep_ld = 0;
+    if constexpr (BUD) { bud_ld = ar.led.budget[envc]; dep_ld = ar.led.depth[envc]; }
+    static_assert(!(BUD && SPLIT), "the budget ledger is a fused-step feature");
     const int* __restrict__ rects = v.colrect + (size_t)envc * v.rank_cap;
     unsigned rc_pre[RJ];
 #pragma unroll
@@ -268,6 +306,9 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_step_patch(
         if (ar.src && tid < kWave) {
             const int k = __builtin_amdgcn_readfirstlane(ar.src[item]);
             if (k >= 0 && h.env >= 0 && h.env < v.cap) wave_reset_env(v, ar, h.env, k, tid);
+        }
+        if constexpr (BUD) {
+            if (tid < kWave) ledger_close(v, ar, flags, h.env, item, v.blk_pos0 + (int)blockIdx.x, bud_ld, dep_ld, h.cost_d, tid);
         }
         return;
     }
@@ -567,6 +608,9 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_step_patch(
     if (lane == 0 && units) { atomicAdd(cnt, units); atomicAdd(cnt + 1, needed); }
     int reset_k = -1;
     if (ar.src) reset_k = __builtin_amdgcn_readfirstlane(ar.src[item]);
+    if constexpr (BUD) {
+        if ((flags & IPP_RESET_ON_DONE) && ledger_done(ar.led, bud_ld, dep_ld, pl.hs->cost_d)) reset_k = 0;
+    }
     // this wave's stores have landed before the last wave rewrites the env's planes (explicit wait, not an agent-scope
     // release fence: that one also writes the XCD's L2 back, once per wave of every resetting item)
     if (reset_k >= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -597,7 +641,8 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_step_patch(
         v.colspan[(size_t)env_u * v.rank_cap + r + lane] = t_span;
         v.colrect[(size_t)env_u * v.rank_cap + r + lane] = (int)rect_pack(r0n, r1n, c0n, c1n);
     }
-    if (reset_k >= 0) wave_reset_env(v, ar, env_u, reset_k, lane);  // (after the rank store above, same lane 0)
+    if constexpr (BUD) ledger_close(v, ar, flags, env_u, item, v.blk_pos0 + (int)blockIdx.x, bud_ld, dep_ld, cost_d, lane);  // (after the rank store above, same lane 0)
+    else if (reset_k >= 0) wave_reset_env(v, ar, env_u, reset_k, lane);  // (after the rank store above, same lane 0)
     IPP_WT(8);
     IPP_WT_FLUSH(lane);
     }

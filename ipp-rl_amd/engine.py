@@ -463,11 +463,14 @@ class IPPEngine:
 
     def step(self, actions, prev_actions, env_ids=None, dst_ids=None, meas_noise=None, *, cov_only=False,
              predict_only=False, adaptive=True, use_flight_time=True, given_observation=False, reward_out=None,
-             status_out=None, update_prev=False, reset_src=None, reset_gt=None, init_action=None):
+             status_out=None, update_prev=False, reset_src=None, reset_gt=None, init_action=None, budget=False,
+             reset_on_done=False):
         """
         One batched env step.  reset_src / reset_gt / init_action (factor engines, in-place committed steps): the
         episode resets that fall on this step, folded into the launch (ipp_step_autoreset): reset_src [n] int32
         device tensor with the index into reset_gt ([k, H, W] float32 device tensor) or -1 per item.
+        budget / reset_on_done (patch-layout engines, full-batch in-place steps): IPP_BUDGET / IPP_RESET_ON_DONE -- the ledger
+        installed by set_budget is charged, and the envs it ends reset in the launch (needs init_action).
         """
         torch = _torch()
         a = self._dev(actions, torch.float64).reshape(-1, 3)
@@ -486,9 +489,18 @@ class IPPEngine:
         status = status_out if status_out is not None else torch.empty(n, dtype=torch.int32, device=self.device)
         flags = (_ffi.IPP_COV_ONLY if cov_only else 0) | (_ffi.IPP_PREDICT_ONLY if predict_only else 0) | \
                 (_ffi.IPP_ADAPTIVE if adaptive else 0) | (_ffi.IPP_USE_FLIGHT_TIME if use_flight_time else 0) | \
-                (_ffi.IPP_GIVEN_OBSERVATION if given_observation else 0) | (_ffi.IPP_UPDATE_PREV if update_prev else 0)
+                (_ffi.IPP_GIVEN_OBSERVATION if given_observation else 0) | (_ffi.IPP_UPDATE_PREV if update_prev else 0) | \
+                (_ffi.IPP_BUDGET if budget else 0) | (_ffi.IPP_RESET_ON_DONE if reset_on_done else 0)
         if update_prev and (predict_only or not isinstance(prev_actions, torch.Tensor) or p.data_ptr() != prev_actions.data_ptr()):
             raise ValueError("update_prev needs prev_actions as a contiguous float64 device tensor and a committed step")
+        if budget or reset_on_done:
+            if reset_on_done and (not isinstance(prev_actions, torch.Tensor) or p.data_ptr() != prev_actions.data_ptr()):
+                raise ValueError("reset_on_done needs prev_actions as a contiguous float64 device tensor (the reset writes it)")
+            init = (C.c_double * 3)(*[float(x) for x in init_action]) if init_action is not None else None
+            _ffi.check(self._lib.ipp_step_autoreset(self._h, self._ptr(ids), n, self._ptr(a), self._ptr(p), self._ptr(nz), flags,
+                                                    self._ptr(reward), self._ptr(status), None, None, init, self.stream))
+            self._keep = (a, p, ids, nz)
+            return reward, status
         if reset_src is not None:
             if dst is not None or predict_only:
                 raise ValueError("reset_src: in-place committed steps only")
@@ -552,6 +564,36 @@ class IPPEngine:
                 ev.record(st)
             ring[4][half] = True
         ring[3] = (i + 1) % 16
+
+    def set_budget(self, budget, depth, episode, done, refill, initial_budget: float, max_steps: int, shuffle_budget: bool = False,
+                   seed: int = 0, row_offset: int = 0):
+        """ipp_set_budget: install the budget ledger of IPP_BUDGET steps -- device tensors budget float64 [capacity], depth int32
+        [capacity], episode int64 [capacity], done uint8 [n], refill int32 [n], kept alive by the reference here (the engine keeps the
+        pointers).  budget=None uninstalls."""
+        if budget is None:
+            self._ledger = None
+            _ffi.check(self._lib.ipp_set_budget(self._h, None, None, None, None, None, 0.0, 0, 0, 0, 0))
+            return
+        torch = _torch()
+        for t, dt in ((budget, torch.float64), (depth, torch.int32), (episode, torch.int64), (done, torch.uint8), (refill, torch.int32)):
+            if not (torch.is_tensor(t) and t.dtype == dt and t.is_cuda and t.is_contiguous()):
+                raise ValueError(f"set_budget: contiguous {dt} device tensors expected")
+        self._ledger = (budget, depth, episode, done, refill)
+        _ffi.check(self._lib.ipp_set_budget(self._h, self._ptr(budget), self._ptr(depth), self._ptr(episode), self._ptr(done),
+                                            self._ptr(refill), float(initial_budget), int(max_steps), int(bool(shuffle_budget)),
+                                            int(seed) & (2 ** 64 - 1), int(row_offset)))
+
+    def generate_grf_refill(self, n: int, refill, episode, seed: int, subsequence: int, row_offset: int = 0, stream=None) -> bool:
+        """ipp_generate_grf_refill: field i into the alternate plane of env refill[i] (negative: skipped), noise subsequence
+        subsequence + episode[env] + 1 (refill / episode: device tensors, e.g. views into the installed ledger).  False: this grid
+        has no generator that draws its own noise."""
+        st = self.stream if stream is None else C.c_void_p(stream.cuda_stream)
+        rc = self._lib.ipp_generate_grf_refill(self._h, int(n), self._ptr(refill), self._ptr(episode), int(row_offset),
+                                               int(seed) & (2 ** 64 - 1), int(subsequence) & (2 ** 64 - 1), st)
+        if rc == -3:
+            return False
+        _ffi.check(rc)
+        return True
 
     def step_raw(self, n, actions, prev_actions, meas_noise, flags, reward, status, env_ids=None):
         """Zero-overhead variant for the benchmark loop: all arguments are preallocated device tensors."""

@@ -29,6 +29,36 @@ from .engine import EngineConfig, IPPEngine
 INIT_ACTION = (2.0, 2.0, 14.0)  # planning/missions.py:69
 
 
+def philox_uniform(counter, subsequence, seed: int) -> np.ndarray:
+    """Philox4x32-10 of (counter, subsequence) under key `seed`, first output word as a uniform in (0, 1): the host copy of the device's
+    draw of a start budget (ipp_common.h, budget_start).  counter / subsequence: int arrays (broadcast)."""
+    m32 = np.uint64(0xFFFFFFFF)
+    q = np.asarray(counter, dtype=np.int64).astype(np.uint64)
+    sub = np.asarray(subsequence, dtype=np.int64).astype(np.uint64)
+    q, sub = np.broadcast_arrays(q, sub)
+    c = [q & m32, q >> np.uint64(32), sub & m32, sub >> np.uint64(32)]
+    k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64((seed >> 32) & 0xFFFFFFFF)
+    with np.errstate(over="ignore"):
+        for _ in range(10):
+            p0 = np.uint64(0xD2511F53) * c[0]
+            p1 = np.uint64(0xCD9E8D57) * c[2]
+            c = [(p1 >> np.uint64(32)) ^ c[1] ^ k0, p1 & m32, (p0 >> np.uint64(32)) ^ c[3] ^ k1, p0 & m32]
+            k0 = (k0 + np.uint64(0x9E3779B9)) & m32
+            k1 = (k1 + np.uint64(0xBB67AE85)) & m32
+    return (c[0].astype(np.float64) + 0.5) * (1.0 / 4294967296.0)
+
+
+def start_budget(initial_budget: float, shuffle_budget: bool, seed: int, global_env_ids, episode) -> np.ndarray:
+    """Start budget of episode `episode` of the given GLOBAL env ids (sample_budget, planning/mcts_zero/episode_generators.py:113):
+    initial_budget, or floor(10 + u (initial_budget - 10)) with u = philox_uniform(env id, IPP_BUDGET_STREAM + episode, seed) -- what
+    the budget step writes on the device when it resets an env."""
+    gid = np.asarray(global_env_ids, dtype=np.int64)
+    if not shuffle_budget:
+        return np.full(gid.shape, float(initial_budget))
+    u = philox_uniform(gid, _ffi.IPP_BUDGET_STREAM + np.asarray(episode, dtype=np.int64), seed)
+    return np.floor(10.0 + u * (float(initial_budget) - 10.0))
+
+
 def shard_range(total: int, rank: int, world: int):
     """Contiguous env-id range of `rank`: [rank*total/world, (rank+1)*total/world)."""
     lo = (total * rank) // world
@@ -60,7 +90,13 @@ class VecIPPEnv:
                  device: str = "cuda:0", seed: int = 1234, env_id_offset: int = 0, shuffle_prior_cov: bool = False,
                  rank_cap: Optional[int] = None, stagger: bool = False, tile_threads: int = 0,
                  adaptive: bool = True, use_flight_time: bool = True, window_rows: int = 0, fused_reset: bool = True,
-                 parts: int = 1, arena=None):
+                 parts: int = 1, arena=None, budget: Optional[float] = None, shuffle_budget: bool = False):
+        """budget=None: episodes of exactly `episode_steps` steps on a schedule known to the host.  budget=B0: the reference's
+        budget-driven episodes (planning/mcts_zero/episode_generators.py:109-150) -- `episode_steps` is max_episode_steps, every env
+        carries a device-side ledger (self.budget, self.depth, self.episode, self.done) that the step kernel charges with the action
+        cost, and an env whose loop condition fails is reset inside the step launch; its next ground truth is generated behind
+        the step from the device's refill list (no device->host sync in the loop).  shuffle_budget: start budgets
+        floor(U(10, B0)) per env and episode (start_budget)."""
         import torch
 
         self.torch = torch
@@ -71,10 +107,29 @@ class VecIPPEnv:
         self.env_id_offset = int(env_id_offset)
         self.shuffle_prior_cov = shuffle_prior_cov
         self.adaptive, self.use_flight_time = adaptive, use_flight_time
+        self.budget_mode = budget is not None
+        self.initial_budget, self.shuffle_budget = (float(budget) if budget is not None else None), bool(shuffle_budget)
+        if self.budget_mode:
+            if shuffle_prior_cov:
+                raise ValueError("budget mode: per-episode shuffled priors are not supported (shuffle_prior_cov)")
+            if state != "factor":
+                raise ValueError("budget mode: patch-layout factor engines only (state='factor')")
+            if cfg.x_dim != cfg.y_dim or cfg.x_dim not in (50, 100):
+                raise ValueError("budget mode: grids whose ground-truth generator draws its own noise only (50x50, 100x100)")
+            if not (self.initial_budget >= cfg.resolution):
+                raise ValueError(f"budget mode: budget {budget} below the grid resolution {cfg.resolution}")
+            if shuffle_budget and not (self.initial_budget >= 10.0):
+                raise ValueError("budget mode: shuffle_budget draws from U(10, budget): budget >= 10 needed")
+        elif shuffle_budget:
+            raise ValueError("shuffle_budget needs budget")
         rank_cap = int(rank_cap) if rank_cap else 9 * self.episode_steps
         self.engine = IPPEngine(cfg, capacity=self.num_envs, state=state, rank_cap=rank_cap, device=device,
                                 tile_threads=tile_threads, window_rows=window_rows, fixed_prior=not shuffle_prior_cov,
                                 arena=arena)
+        if self.budget_mode and (int(self.engine.info.patch_layout) != 1 or int(self.engine.info.fused_step) != 1):
+            self.engine.close()
+            raise ValueError("budget mode: patch-layout engines only (windowed factor state, ipp_info.patch_layout == 1)")
+        sched = stagger and not self.budget_mode  # the fixed reset schedule and its structures
         dev = self.engine.device
         self.device = dev
         B = self.num_envs
@@ -89,7 +144,7 @@ class VecIPPEnv:
         # dispatch orders of the step launches, one per schedule phase (staggered runs): env e has done (t + phase_e) % T steps
         # of its episode when step t starts; descending = longest items first (engine.set_item_order)
         self._orders = None
-        if stagger and os.environ.get("IPP_ITEM_ORDER", "1") != "0":
+        if sched and os.environ.get("IPP_ITEM_ORDER", "1") != "0":
             ph = (np.arange(B, dtype=np.int64) + self.env_id_offset) % self.episode_steps
             self._orders = [torch.as_tensor(np.argsort(-((t + ph) % self.episode_steps), kind="stable").astype(np.int32), device=dev)
                             for t in range(self.episode_steps)]
@@ -116,8 +171,10 @@ class VecIPPEnv:
             self._ev_inputs = torch.cuda.Event()
             self._async_pending = False
             self._main_dirty = True  # the caller's stream holds work on the env slots that the part streams have not waited for
+        if self.budget_mode:
+            self._init_budget_parts(parts)
         self._reset_ids_by_phase = None
-        if stagger:
+        if sched:
             ph = self.phase.cpu().numpy()
             self._reset_ids_host = [np.nonzero(ph == p)[0].astype(np.int32) for p in range(self.episode_steps)]
             self._reset_ids_by_phase = [torch.as_tensor(i, device=dev) for i in self._reset_ids_host]
@@ -132,7 +189,7 @@ class VecIPPEnv:
         # (with shuffled priors the folded form is available -- fused_reset="always" -- but not the default: measured equal
         # to the separate launch, 19.4-19.5 vs 19.3-20.3 M env-steps/s at window 12; a partitioned env takes it: step_async needs the
         # resets inside the step launches)
-        self._fused_reset = bool(fused_reset and stagger and state == "factor" and
+        self._fused_reset = bool(fused_reset and sched and state == "factor" and
                                  (not shuffle_prior_cov or fused_reset == "always" or self.parts > 1) and
                                  self.engine.info.fused_step == 1 and self.engine.info.window_rows > 0 and
                                  4 * B * self.episode_steps <= (64 << 20))
@@ -143,7 +200,7 @@ class VecIPPEnv:
         # (the GRF convolution is fp64-compute-bound, the step is HBM-bound: they overlap on the chip); the field
         # for the resets after step t+1 is started at the beginning of step t, so it has two steps to finish
         self._side = None
-        if stagger:
+        if sched:
             self._side = self._side_pick if self._part_streams is not None else self._pick_streams(dev, 1)[1]
         self._grf_rows = None if os.environ.get("IPP_GRF_ROWS", "1") != "0" else False  # (False: the engine has no in-generator noise / A/B)
         self._gt_flip_ok = os.environ.get("IPP_GT_FLIP", "1") != "0"  # (A/B: 0 = staged buffers + copies at the resets)
@@ -154,7 +211,7 @@ class VecIPPEnv:
         # wait and an event record per step the stream protocol cost 12-20 us of every step (4096 envs of 50x50: 0.186 ms per
         # step against 0.171 without events, profiles/r02_experiments.txt).  2 K <= episode_steps: within the staging
         # horizon an env resets at most once, so its episode counter read at staging time names the right ground truth.
-        if stagger:
+        if sched:
             n_max = max(int(i.numel()) for i in self._reset_ids_by_phase)
             # (cap of the two staged sets: 2 GiB -- with 256 MiB configs[2], 2048 resets of 40 KB per step, staged block by block of ONE step
             # and paid the streams' meeting every step: 0.4695 against 0.4436 ms per step with blocks of eight, profiles/r06_experiments.txt 14)
@@ -194,6 +251,88 @@ class VecIPPEnv:
         self.reward = torch.empty(B, dtype=torch.float32, device=dev)
         self.status = torch.empty(B, dtype=torch.int32, device=dev)
         self._flags = (4 if adaptive else 0) | (8 if use_flight_time else 0)
+        if self.budget_mode:
+            # the ledger (ipp_set_budget): per env the remaining budget, the steps taken and the current episode's index; per item of the
+            # last step the done flag, per dispatch position the env that reset there (-1: none) -- the generator's refill list
+            self.budget = torch.zeros(B, dtype=torch.float64, device=dev)
+            self.depth = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.episode = torch.zeros(B, dtype=torch.int64, device=dev)
+            self.done = torch.zeros(B, dtype=torch.uint8, device=dev)
+            self.refill = torch.full((B,), -1, dtype=torch.int32, device=dev)
+            self._started = False
+            self.engine.set_budget(self.budget, self.depth, self.episode, self.done, self.refill, self.initial_budget,
+                                   self.episode_steps, self.shuffle_budget, self.seed, self.env_id_offset)
+
+    def _init_budget_parts(self, parts: int):
+        """Budget mode, parts > 1: the fixed env groups of the scheduled mode (env e in group ((e + env_id_offset) // episode_steps) % parts),
+        items in env-id order within a part (no device-side ordering by weight: the steps since an env's reset are not known on the host)."""
+        torch, B, dev = self.torch, self.num_envs, self.device
+        self._budget_order = None
+        if parts <= 1 or B < 2 * parts:
+            return
+        grp = ((np.arange(B, dtype=np.int64) + self.env_id_offset) // self.episode_steps) % int(parts)
+        counts = np.bincount(grp, minlength=int(parts))
+        if np.any(counts == 0):
+            return
+        self.parts = int(parts)
+        self._budget_order = torch.as_tensor(np.argsort(grp, kind="stable").astype(np.int32), device=dev)
+        self._part_begin = [0] + [int(x) for x in np.cumsum(counts)]
+        self._part_envs = [torch.as_tensor(np.nonzero(grp == g)[0].astype(np.int64), device=dev) for g in range(self.parts)]
+        self._part_streams, self._side_pick = self._pick_streams(dev, self.parts)
+        self._part_done = [torch.cuda.Event() for _ in range(self.parts)]
+        self._ev_inputs = torch.cuda.Event()
+        self._async_pending = False
+        self._main_dirty = True
+
+    def _reset_budget(self, env_ids, white_noise, gt, prior_scale):
+        """reset() in budget mode: every env starts its next episode (the first call: episode 0) with a fresh ledger -- the start budget,
+        depth = its stagger phase -- and the field of the episode after it staged in its alternate plane."""
+        torch = self.torch
+        if env_ids is not None or white_noise is not None or gt is not None or prior_scale is not None:
+            raise ValueError("budget mode: reset() resets every env with its own ground truths (no env_ids / white_noise / gt / prior_scale)")
+        if self.parts > 1:
+            self.wait()
+            self._main_dirty = True
+        B = self.num_envs
+        epi = (self.episode.cpu().numpy() + 1) if self._started else np.zeros(B, dtype=np.int64)
+        gid = np.arange(B, dtype=np.int64) + self.env_id_offset
+        for e in np.unique(epi):
+            sel = np.nonzero(epi == e)[0].astype(np.int32)
+            ids = torch.as_tensor(sel, device=self.device)
+            white = self._white[:len(sel)]
+            self.engine.normal_rows(white, self.cfg.n_cells, self.seed, self.GT_STREAM + int(e), row_ids=ids, row_offset=self.env_id_offset)
+            self.engine.reset(env_ids=ids, white_noise=white, prev=self.prev, init_action=INIT_ACTION)
+            # the next episode's field into the alternate planes: a reset on done flips to it
+            self.engine.generate_grf_rows(len(sel), self.seed, self.GT_STREAM + int(e) + 1, None, row_ids=ids, row_offset=self.env_id_offset)
+        self.episode.copy_(torch.as_tensor(epi, device=self.device))
+        self.budget.copy_(torch.as_tensor(start_budget(self.initial_budget, self.shuffle_budget, self.seed, gid, epi), device=self.device))
+        self.depth.copy_(self.phase.to(torch.int32))
+        self.done.zero_()
+        self.refill.fill_(-1)
+        self._started = True
+
+    def _step_budget(self, actions, meas_noise, auto_reset: bool):
+        """One budget-mode step of the whole batch (parts == 1): the ledger is charged in the step launch, the envs it ends reset there
+        (auto_reset), and the generator stages their next fields behind it on the same stream."""
+        torch = self.torch
+        a = self.engine._dev(actions, torch.float64).reshape(-1, 3)
+        nz = meas_noise if meas_noise is not None else self._noise_plane_single()
+        self.engine.step(a, self.prev, meas_noise=nz, adaptive=self.adaptive, use_flight_time=self.use_flight_time,
+                         reward_out=self.reward, status_out=self.status, update_prev=True, budget=True, reset_on_done=auto_reset,
+                         init_action=INIT_ACTION)
+        if auto_reset:
+            self.engine.generate_grf_refill(self.num_envs, self.refill, self.episode, self.seed, self.GT_STREAM, row_offset=self.env_id_offset)
+        self.t += 1
+        return self.reward, self.status
+
+    def _noise_plane_single(self):
+        if self._noise_pos == 0:
+            self.engine.normal_rows(self._noise_ring, self.engine.meas_cap, self.seed, self.NOISE_STREAM +
+                                    self._noise_fills * self.NOISE_RING, row_offset=self.env_id_offset)
+            self._noise_fills += 1
+        nz = self._noise_ring[self._noise_pos]
+        self._noise_pos = (self._noise_pos + 1) % self.NOISE_RING
+        return nz
 
     # ------------------------------------------------------------------ resets
     def _prior_scale(self, ids_host: np.ndarray, episode_index):
@@ -238,6 +377,8 @@ class VecIPPEnv:
     def reset(self, env_ids=None, white_noise=None, gt=None, prior_scale=None, _phase=None):
         """Reset the given slots (all when None).  white_noise / gt: [n, H, W] NumPy or tensor (parity)."""
         torch = self.torch
+        if self.budget_mode:
+            return self._reset_budget(env_ids, white_noise, gt, prior_scale)
         if self.parts > 1:
             self.wait()
             self._main_dirty = True
@@ -444,6 +585,16 @@ class VecIPPEnv:
         schedule known to the host (no device->host sync in the loop).
         """
         torch = self.torch
+        if self.budget_mode:
+            if env_ids is not None or after_step_hook is not None:
+                raise ValueError("budget mode: full-batch steps only (no env_ids / after_step_hook)")
+            if self.parts > 1:
+                if meas_noise is not None or not auto_reset:
+                    raise ValueError("budget mode with parts > 1: device noise and auto_reset only")
+                self.step_async(actions)
+                self.wait()
+                return self.reward, self.status
+            return self._step_budget(actions, meas_noise, auto_reset)
         if self.parts > 1:
             if env_ids is None and auto_reset and meas_noise is None and after_step_hook is None and \
                     (self._fused_reset or self._reset_ids_by_phase is None):
@@ -633,6 +784,8 @@ class VecIPPEnv:
         torch = self.torch
         if self.parts <= 1:
             raise RuntimeError("step_async needs VecIPPEnv(parts > 1, stagger=True) on a fused-step engine")
+        if self.budget_mode:
+            return self._step_async_budget(actions, inputs_ready)
         if not (self._fused_reset or self._reset_ids_by_phase is None):
             raise RuntimeError("step_async needs the scheduled resets inside the step launch (fused_reset)")
         a = actions if (torch.is_tensor(actions) and actions.dtype == torch.float64 and actions.is_cuda and actions.is_contiguous()) \
@@ -682,6 +835,30 @@ class VecIPPEnv:
         self._async_pending = True
         if prefetch is not None:
             self._prefetch_next_block(*prefetch)
+
+    def _step_async_budget(self, actions, inputs_ready: bool):
+        """step_async in budget mode: the part launches charge the ledger and reset the envs it ends; behind each, on its stream, the
+        generator stages the next fields of that part's resets (its range of refill positions)."""
+        torch = self.torch
+        a = actions if (torch.is_tensor(actions) and actions.dtype == torch.float64 and actions.is_cuda and actions.is_contiguous()) \
+            else self.engine._dev(actions, torch.float64).reshape(-1, 3).contiguous()
+        streams = self._part_streams
+        if not inputs_ready or self._main_dirty:
+            self._main_dirty = False
+            self._ev_inputs.record(torch.cuda.current_stream(self.device))
+            for st in streams:
+                st.wait_event(self._ev_inputs)
+        nz = self._noise_plane_parts(None if self._noise_pos else torch.cuda.current_stream(self.device), streams)
+        self.engine.set_item_order(self._budget_order)
+        self.engine.step_parts(a, self.prev, nz, self._flags | _ffi.IPP_UPDATE_PREV | _ffi.IPP_BUDGET | _ffi.IPP_RESET_ON_DONE, self.reward,
+                               self.status, self._part_begin, streams, init_action=INIT_ACTION)
+        for p, st in enumerate(streams):
+            b, e = self._part_begin[p], self._part_begin[p + 1]
+            self.engine.generate_grf_refill(e - b, self.refill[b:e], self.episode, self.seed, self.GT_STREAM, row_offset=self.env_id_offset,
+                                            stream=st)
+        self._noise_done_parts(streams)
+        self.t += 1
+        self._async_pending = True
 
     def _noise_plane_parts(self, main, streams):
         """Measurement noise of this step on a partitioned batch: plane `pos` of ring (fill index % 2); the other ring is

@@ -27,11 +27,18 @@
 extern "C" {
 #endif
 
-#define IPP_ABI_VERSION 15
+#define IPP_ABI_VERSION 16
 
 /* covariance state representation */
 #define IPP_DENSE  0 /* P[N][N] fp32 per env, updated in place (mapping/grid_maps.py:10-11)         */
 #define IPP_FACTOR 1 /* P = P0(sigma^2, l) - U U^T, U[N][r] fp32 grows by m columns per step         */
+
+/* prior covariance functions (ipp_engine_create_prior): sigma^2 * Matern(l, nu) with d the distance of two cell centres in
+ * metres, in the closed forms of sklearn.gaussian_process.kernels.Matern (mapping/mappings.py:236-261, config mapping.nu) */
+#define IPP_PRIOR_MATERN32 0 /* nu = 1.5: (1 + t) exp(-t), t = sqrt(3) d / l   (the default)  */
+#define IPP_PRIOR_MATERN12 1 /* nu = 0.5: exp(-d / l)                                         */
+#define IPP_PRIOR_MATERN52 2 /* nu = 2.5: (1 + t + t^2 / 3) exp(-t), t = sqrt(5) d / l         */
+#define IPP_PRIOR_RBF      3 /* nu = inf: exp(-d^2 / (2 l^2))                                  */
 
 /* ipp_step flags */
 #define IPP_COV_ONLY        1u /* no observation / mean update     (mappings.py:114 cov_only=True)        */
@@ -163,6 +170,21 @@ int ipp_engine_arena_bytes(const ipp_config* cfg, uint64_t* bytes /*[host]*/);
  */
 int ipp_engine_create(const ipp_config* cfg, int device, void* arena /*[dev]*/, uint64_t arena_bytes,
                       void** engine /*[host] out*/);
+
+/*
+ * The three calls above for a prior of kind IPP_PRIOR_* (they are these calls with IPP_PRIOR_MATERN32).  The prior of
+ * every reset, table and dense read of the engine is then sigma^2 * k(d) of that kind.  Replaces: the
+ * ConstantKernel(sigma^2) * Matern(length_scale, nu=mapping.nu) prior of Mapping.init_priors, evaluated through an
+ * unfitted GaussianProcessRegressor (mapping/mappings.py:236-261, config/example.yaml:27 nu) for the four nu that
+ * sklearn evaluates in closed form.  window_rows is checked against the kind's own decay: the smallest R with
+ * sigma^2 k(R resolution; l_max) <= 1e-6 (ipp_min_window_rows_prior; 14 / 10 / 8 rows for nu = 0.5 / 1.5 / 2.5 of the
+ * example config with fixed_prior = 1, 16 / 12 / 10 without).  RBF takes the Matern 3/2 rule (10 / 12): the RBF gain columns
+ * reach further than its prior (ipp_engine.hip, window_bound).  An unknown kind fails (ipp_last_error).
+ */
+int ipp_min_window_rows_prior(const ipp_config* cfg, int32_t kind, int32_t* rows /*[host]*/);
+int ipp_engine_arena_bytes_prior(const ipp_config* cfg, int32_t kind, uint64_t* bytes /*[host]*/);
+int ipp_engine_create_prior(const ipp_config* cfg, int32_t kind, int device, void* arena /*[dev]*/, uint64_t arena_bytes,
+                            void** engine /*[host] out*/);
 int ipp_engine_destroy(void* engine);
 int ipp_engine_info(void* engine, ipp_info* out /*[host]*/);
 

@@ -11,13 +11,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("IPP_HIP_LIB") or os.path.join(_HERE, "lib", "libipp_hip.so")  # override: A/B builds only
 
 IPP_DENSE, IPP_FACTOR = 0, 1
+IPP_PRIOR_MATERN32, IPP_PRIOR_MATERN12, IPP_PRIOR_MATERN52, IPP_PRIOR_RBF = 0, 1, 2, 3
 IPP_COV_ONLY, IPP_PREDICT_ONLY, IPP_ADAPTIVE, IPP_USE_FLIGHT_TIME, IPP_GIVEN_OBSERVATION, IPP_UPDATE_PREV = 1, 2, 4, 8, 16, 32
 IPP_BUDGET, IPP_RESET_ON_DONE = 64, 128
 IPP_BUDGET_STREAM = 3 << 40
 STATUS_OK, STATUS_CHOL_FALLBACK, STATUS_NOT_PD, STATUS_RANK_FULL, STATUS_BAD_FOOTPRINT = 0, 1, 2, 3, 4
 IPP_MAX_MEAS = 25
-ABI_VERSION = 15
-AB_MIN_ABI = 13  # oldest library tools/ab_kernels.py may load under IPP_AB_OLD_LIB (v14 added the ipp_arena_* calls, v15 the budget ledger calls; nothing else)
+ABI_VERSION = 16
+AB_MIN_ABI = 13  # oldest library tools/ab_kernels.py may load under IPP_AB_OLD_LIB (v14 added the ipp_arena_* calls, v15 the budget ledger calls, v16 the *_prior calls; nothing else)
 IPP_ARENA_HIPMALLOC, IPP_ARENA_VMM = 0, 1
 
 
@@ -95,6 +96,9 @@ PROTOTYPES = {
     "ipp_last_error": (C.c_char_p, []),
     "ipp_engine_arena_bytes": (C.c_int, [C.POINTER(IppConfig), C.POINTER(C.c_uint64)]),
     "ipp_engine_create": (C.c_int, [C.POINTER(IppConfig), C.c_int, _P, C.c_uint64, C.POINTER(_P)]),
+    "ipp_min_window_rows_prior": (C.c_int, [C.POINTER(IppConfig), C.c_int32, _P]),
+    "ipp_engine_arena_bytes_prior": (C.c_int, [C.POINTER(IppConfig), C.c_int32, C.POINTER(C.c_uint64)]),
+    "ipp_engine_create_prior": (C.c_int, [C.POINTER(IppConfig), C.c_int32, C.c_int, _P, C.c_uint64, C.POINTER(_P)]),
     "ipp_engine_destroy": (C.c_int, [_P]),
     "ipp_engine_info": (C.c_int, [_P, C.POINTER(IppInfo)]),
     "ipp_reset": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),

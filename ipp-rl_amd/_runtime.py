@@ -44,7 +44,7 @@ def state_slots_for(n_cells: int) -> int:
 
 def config_key(cfg: EngineConfig) -> Tuple:
     return (cfg.x_dim, cfg.y_dim, cfg.resolution, cfg.angle_x, cfg.angle_y, cfg.rf_altitude, cfg.coeff_a, cfg.coeff_b,
-            cfg.signal_variance, cfg.length_scale, cfg.cluster_radius)
+            cfg.signal_variance, cfg.length_scale, cfg.cluster_radius, cfg.nu)
 
 
 def compat_engine(cfg: EngineConfig) -> IPPEngine:
@@ -85,9 +85,11 @@ def on_device(eng: IPPEngine, state) -> DeviceCov:
     return obj
 
 
-def engine_config_from(grid_map, sensor, signal_variance: float, length_scale: float, cluster_radius=None) -> EngineConfig:
+def engine_config_from(grid_map, sensor, signal_variance: float, length_scale: float, cluster_radius=None,
+                       nu: float = 1.5) -> EngineConfig:
     """cluster_radius: the simulation passes its own (it builds its first ground truth BEFORE it is attached to the
-    sensor: planning/ipp_mission_node.py:40-42, simulations/simulations.py:41); the mapping takes the attached one."""
+    sensor: planning/ipp_mission_node.py:40-42, simulations/simulations.py:41); the mapping takes the attached one.
+    nu: Matern smoothness of the prior (prior_nu)."""
     cluster = cluster_radius
     if cluster is None:
         cluster = getattr(getattr(sensor, "sensor_simulation", None), "cluster_radius", None)
@@ -96,8 +98,17 @@ def engine_config_from(grid_map, sensor, signal_variance: float, length_scale: f
         angle_x=float(sensor.angle_x), angle_y=float(sensor.angle_y),
         coeff_a=float(sensor.sensor_model.coeff_a), coeff_b=float(sensor.sensor_model.coeff_b),
         signal_variance=float(signal_variance), length_scale=float(length_scale),
-        cluster_radius=float(cluster) if cluster is not None else 5.0,
+        cluster_radius=float(cluster) if cluster is not None else 5.0, nu=float(nu),
     )
+
+
+def prior_nu(mapping_params) -> float:
+    """nu of the compat engine for a config's `mapping` section: mapping.nu for the GP prior; the non-GP prior
+    (fit_gaussian_process: false) never evaluates the kernel and keeps the default, so Mapping and the simulation
+    share one engine either way."""
+    if not mapping_params.get("fit_gaussian_process", True):
+        return 1.5
+    return float(mapping_params.get("nu", 1.5))
 
 
 def to_host64(t) -> np.ndarray:

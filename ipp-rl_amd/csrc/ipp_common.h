@@ -176,6 +176,7 @@ struct View {
     double* grf_amp; // [NP][NP] spectral amplitude, zero padded  (k_grf_hartley.h)
     float* grf_raw;  // [max_batch][Npad] un-normalised field (ipp_reset)
     float* grf_raw2; // [max_batch][Npad] un-normalised field (ipp_generate_grf, may run on a side stream)
+    int prior_kind;  // IPP_PRIOR_*: the covariance function of the prior (uniform; kept last, after the fields the kernels read per cell)
 };
 
 // The plane that holds env's ground truth / the one that is staged for its next episode.
@@ -409,6 +410,66 @@ __device__ __forceinline__ double matern_d(int dr, int dc, double res, double sv
 __device__ __forceinline__ float matern_f(int dr, int dc, float res_s3_over_ls, float sv) {
     const float t = res_s3_over_ls * sqrtf((float)(dr * dr + dc * dc));
     return sv * (1.0f + t) * __expf(-t);
+}
+
+// The other priors of ipp_engine_create_prior: sigma^2 * Matern(l, nu) for nu = 1/2, 5/2 and inf, in the closed forms of
+// sklearn.gaussian_process.kernels.Matern.__call__ with u = d / l the scaled distance (mapping/mappings.py:242-258 with
+// mapping.nu).  K is the IPP_PRIOR_* kind; kind 0 is matern_d / matern_f above, unchanged.
+constexpr double kSqrt5 = 2.23606797749979;
+template <int K>
+__device__ __forceinline__ double prior_d(int dr, int dc, double res, double sv, double ls) {
+    if constexpr (K == IPP_PRIOR_MATERN32) {
+        return matern_d(dr, dc, res, sv, ls);
+    } else {
+        const double u = res * sqrt((double)(dr * dr + dc * dc)) / ls;
+        if constexpr (K == IPP_PRIOR_MATERN12) {
+            return sv * exp(-u);
+        } else if constexpr (K == IPP_PRIOR_MATERN52) {
+            const double t = u * kSqrt5;
+            return sv * ((1.0 + t + t * t / 3.0) * exp(-t));
+        } else {
+            return sv * exp(-(u * u) / 2.0);
+        }
+    }
+}
+// fp32: `a` = prior_scale_f(kind, res, l), the factor of the cell distance sqrt(dr^2 + dc^2) in the exponent
+template <int K>
+__device__ __forceinline__ float prior_f(int dr, int dc, float a, float sv) {
+    if constexpr (K == IPP_PRIOR_MATERN32) {
+        return matern_f(dr, dc, a, sv);
+    } else if constexpr (K == IPP_PRIOR_RBF) {
+        const float q = a * a * (float)(dr * dr + dc * dc);
+        return sv * __expf(-0.5f * q);
+    } else {
+        const float t = a * sqrtf((float)(dr * dr + dc * dc));
+        if constexpr (K == IPP_PRIOR_MATERN12) return sv * __expf(-t);
+        else return sv * (1.0f + t + t * t * (1.0f / 3.0f)) * __expf(-t);
+    }
+}
+__device__ __forceinline__ float prior_scale_f(int kind, double res, float ls) {
+    if (kind == IPP_PRIOR_MATERN32) return (float)(kSqrt3 * res) / ls;
+    if (kind == IPP_PRIOR_MATERN52) return (float)(kSqrt5 * res) / ls;
+    return (float)res / ls;
+}
+// Calls f(std::integral_constant<int, kind>) once: loops over cells go inside f, so that the kind is decided once per loop
+// (v.prior_kind is uniform), not per cell.
+template <typename F>
+__device__ __forceinline__ void with_prior_kind(int kind, F&& f) {
+    switch (kind) {
+    case IPP_PRIOR_MATERN12: f(std::integral_constant<int, IPP_PRIOR_MATERN12>{}); break;
+    case IPP_PRIOR_MATERN52: f(std::integral_constant<int, IPP_PRIOR_MATERN52>{}); break;
+    case IPP_PRIOR_RBF: f(std::integral_constant<int, IPP_PRIOR_RBF>{}); break;
+    default: f(std::integral_constant<int, IPP_PRIOR_MATERN32>{}); break;
+    }
+}
+// one evaluation (ktab entries, dense readers): the kind as a uniform branch
+__device__ __forceinline__ double prior_d(int kind, int dr, int dc, double res, double sv, double ls) {
+    switch (kind) {
+    case IPP_PRIOR_MATERN12: return prior_d<IPP_PRIOR_MATERN12>(dr, dc, res, sv, ls);
+    case IPP_PRIOR_MATERN52: return prior_d<IPP_PRIOR_MATERN52>(dr, dc, res, sv, ls);
+    case IPP_PRIOR_RBF: return prior_d<IPP_PRIOR_RBF>(dr, dc, res, sv, ls);
+    default: return matern_d(dr, dc, res, sv, ls);
+    }
 }
 
 // Measurement block i of the footprint (sensors/models/sensor_models.py:57-79).

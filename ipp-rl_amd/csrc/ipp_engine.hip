@@ -177,20 +177,40 @@ int patch_waves_wanted() {
 }
 
 // Windowed factor columns: the largest length scale a reset may install and the prior covariance dropped at the
-// window edge for it (Matern 3/2 at R rows).
+// window edge for it (the prior of `kind` at R rows; every kind decays monotonically in the distance).  The RBF prior
+// takes the Matern 3/2 rule: its own tail is below 1e-6 at 5 rows (example prior, 4 m cells), but the columns a step
+// appends are P H^T L^-1, and for this smoothest kernel L^-1 of a footprint of neighbouring cells is large -- cut at 5
+// rows, the 40-step episode_rf1_50_s0 drifts 1.2e-3 from exact columns in the mean, at 7 rows 1.3e-5, at 10 rows 6e-8
+// (dense NumPy model of the window), while Matern 1/2 and 5/2 at their own windows stay below 3e-6.
 constexpr double kWindowBound = 1e-6;
-double max_length_scale(const ipp_config& c) { return (c.fixed_prior ? 1.0 : 1.2) * c.length_scale; }
-double window_bound(const ipp_config& c, int rows) {
-    const double a = std::sqrt(3.0) * (double)rows * c.resolution / max_length_scale(c);
-    return c.signal_variance * (1.0 + a) * std::exp(-a);
+bool prior_kind_ok(int kind) { return kind >= IPP_PRIOR_MATERN32 && kind <= IPP_PRIOR_RBF; }
+const char* prior_kind_name(int kind) {
+    switch (kind) {
+    case IPP_PRIOR_MATERN12: return "Matern nu=0.5";
+    case IPP_PRIOR_MATERN52: return "Matern nu=2.5";
+    case IPP_PRIOR_RBF: return "RBF (Matern nu=inf)";
+    default: return "Matern nu=1.5";
+    }
 }
-int min_window_rows(const ipp_config& c) {
+double max_length_scale(const ipp_config& c) { return (c.fixed_prior ? 1.0 : 1.2) * c.length_scale; }
+double window_bound(const ipp_config& c, int kind, int rows) {
+    if (kind == IPP_PRIOR_MATERN32 || kind == IPP_PRIOR_RBF) {
+        const double a = std::sqrt(3.0) * (double)rows * c.resolution / max_length_scale(c);
+        return c.signal_variance * (1.0 + a) * std::exp(-a);
+    }
+    const double u = (double)rows * c.resolution / max_length_scale(c);
+    if (kind == IPP_PRIOR_MATERN12) return c.signal_variance * std::exp(-u);
+    const double t = std::sqrt(5.0) * u;  // IPP_PRIOR_MATERN52
+    return c.signal_variance * (1.0 + t + t * t / 3.0) * std::exp(-t);
+}
+int min_window_rows(const ipp_config& c, int kind) {
     int r = 1;
-    while (r < (1 << 20) && window_bound(c, r) > kWindowBound) ++r;
+    while (r < (1 << 20) && window_bound(c, kind, r) > kWindowBound) ++r;
     return r;
 }
 
-int plan(const ipp_config& c, Layout& L, bool allow_patch = true) {
+int plan(const ipp_config& c, int kind, Layout& L, bool allow_patch = true) {
+    if (!prior_kind_ok(kind)) return fail(-1, "unknown prior kind %d (IPP_PRIOR_MATERN32 / MATERN12 / MATERN52 / RBF)", kind);
     if (c.x_dim <= 0 || c.y_dim <= 0) return fail(-1, "x_dim/y_dim must be positive");
     if (!(c.resolution > 0)) return fail(-1, "resolution must be positive");
     if (c.state_repr != IPP_DENSE && c.state_repr != IPP_FACTOR) return fail(-1, "state_repr must be IPP_DENSE or IPP_FACTOR");
@@ -240,11 +260,11 @@ int plan(const ipp_config& c, Layout& L, bool allow_patch = true) {
     if (c.state_repr == IPP_FACTOR && c.window_rows > 0) {
         // the columns are cut where the prior covariance to the footprint has decayed: refuse windows that are too
         // narrow for this prior (length scale up to 1.2 x nominal under shuffle_prior_cov, mappings.py:238-240)
-        const double bound = window_bound(c, c.window_rows);
+        const double bound = window_bound(c, kind, c.window_rows);
         if (c.window_rows < std::max(c.x_dim, c.y_dim) && bound > kWindowBound)
-            return fail(-1, "window_rows = %d drops prior covariances up to %.1e (> 1e-6) for length scales up to %.3g m at %.3g m cells: "
-                            "use window_rows >= %d, or 0 for exact columns", c.window_rows, bound, max_length_scale(c), c.resolution,
-                        min_window_rows(c));
+            return fail(-1, "window_rows = %d drops prior covariances up to %.1e (> 1e-6) for length scales up to %.3g m at %.3g m cells "
+                            "(%s prior): use window_rows >= %d, or 0 for exact columns", c.window_rows, bound, max_length_scale(c),
+                        c.resolution, prior_kind_name(kind), min_window_rows(c, kind));
         // windowed factor state: one workgroup per item, wave-granular tiles of 64 * VEC cells (k_gain_factor.h);
         // tile_threads is the workgroup size (waves share the item's Q block and prior table in LDS)
         L.T = (c.tile_threads > 0) ? c.tile_threads : 256;  // 256: fused workgroup kernel (k_step_factor.h), 64: one wave per item (k_gain_wave.h)
@@ -328,7 +348,7 @@ int plan(const ipp_config& c, Layout& L, bool allow_patch = true) {
         // tree kernels take over
         if (L.patch && allow_patch) {
             const uint64_t reach = (L.off_tr_diag - L.off_cov) + (uint64_t)kTreePatchGuard + (1ull << 20);  // (+ the largest shift of a patch)
-            if (reach >= (1ull << 35)) return plan(c, L, false);
+            if (reach >= (1ull << 35)) return plan(c, kind, L, false);
         }
     }
     L.total = o;
@@ -767,25 +787,31 @@ extern "C" {
 int ipp_abi_version(void) { return IPP_ABI_VERSION; }
 const char* ipp_last_error(void) { return g_err.c_str(); }
 
-int ipp_min_window_rows(const ipp_config* cfg, int32_t* rows) {
+int ipp_min_window_rows_prior(const ipp_config* cfg, int32_t kind, int32_t* rows) {
     if (!cfg || !rows) return fail(-1, "null argument");
+    if (!prior_kind_ok(kind)) return fail(-1, "unknown prior kind %d (IPP_PRIOR_MATERN32 / MATERN12 / MATERN52 / RBF)", kind);
     if (!(cfg->resolution > 0) || !(cfg->length_scale > 0) || !(cfg->signal_variance > 0)) return fail(-1, "resolution, length_scale and signal_variance must be positive");
-    *rows = min_window_rows(*cfg);
+    *rows = min_window_rows(*cfg, kind);
     return 0;
 }
+int ipp_min_window_rows(const ipp_config* cfg, int32_t* rows) { return ipp_min_window_rows_prior(cfg, IPP_PRIOR_MATERN32, rows); }
 
-int ipp_engine_arena_bytes(const ipp_config* cfg, uint64_t* bytes) {
+int ipp_engine_arena_bytes_prior(const ipp_config* cfg, int32_t kind, uint64_t* bytes) {
     if (!cfg || !bytes) return fail(-1, "null argument");
     Layout L;
-    if (int rc = plan(*cfg, L)) return rc;
+    if (int rc = plan(*cfg, kind, L)) return rc;
     *bytes = L.total;
     return 0;
 }
+int ipp_engine_arena_bytes(const ipp_config* cfg, uint64_t* bytes) { return ipp_engine_arena_bytes_prior(cfg, IPP_PRIOR_MATERN32, bytes); }
 
 int ipp_engine_create(const ipp_config* cfg, int device, void* arena, uint64_t arena_bytes, void** engine) {
+    return ipp_engine_create_prior(cfg, IPP_PRIOR_MATERN32, device, arena, arena_bytes, engine);
+}
+int ipp_engine_create_prior(const ipp_config* cfg, int32_t kind, int device, void* arena, uint64_t arena_bytes, void** engine) {
     if (!cfg || !arena || !engine) return fail(-1, "null argument");
     Layout L;
-    if (int rc = plan(*cfg, L)) return rc;
+    if (int rc = plan(*cfg, kind, L)) return rc;
     if (arena_bytes < L.total) return fail(-1, "arena too small: %llu < %llu", (unsigned long long)arena_bytes, (unsigned long long)L.total);
     if ((reinterpret_cast<uintptr_t>(arena) & (kAlign - 1)) != 0) return fail(-1, "arena must be %llu-byte aligned", (unsigned long long)kAlign);
     HIP_TRY(hipSetDevice(device));
@@ -802,6 +828,7 @@ int ipp_engine_create(const ipp_config* cfg, int device, void* arena, uint64_t a
     v.coeff_a = cfg->coeff_a; v.coeff_b = cfg->coeff_b; v.sv0 = cfg->signal_variance; v.ls0 = cfg->length_scale;
     v.ls_max = (cfg->state_repr == IPP_FACTOR && cfg->window_rows > 0 && cfg->window_rows < std::max(cfg->x_dim, cfg->y_dim)) ? max_length_scale(*cfg) : 0.0;
     v.vmax = cfg->max_v; v.amax = cfg->max_a; v.thr = cfg->value_threshold; v.kf = cfg->interval_factor;
+    v.prior_kind = kind;
     char* base = reinterpret_cast<char*>(arena);
     v.mean = reinterpret_cast<float*>(base + L.off_mean);
     v.diag = reinterpret_cast<float*>(base + L.off_diag);

@@ -210,16 +210,19 @@ __global__ __launch_bounds__(kMaxTileThreads, IPP_MINWAVES) void k_gain(View v, 
     // the workgroup tabulates it once in LDS (aliasing the Q staging area) instead of evaluating sqrt/exp
     // for every (cell, footprint cell) pair; grids too large for the table evaluate it directly.
     if (MODE == IPP_FACTOR) {
-        const float s3 = (float)(kSqrt3 * v.res) / h.ls;
+        const float s3 = prior_scale_f(v.prior_kind, v.res, h.ls);
         const bool use_lut = v.N <= lut_cap;
         float* lut = Qs;
         if (use_lut) {
+            with_prior_kind(v.prior_kind, [&](auto kind) {
             for (int i = tid; i < v.N; i += T) {
                 const int dr = i / v.W, dc = i - dr * v.W;
-                lut[i] = matern_f(dr, dc, s3, h.sv);
+                lut[i] = prior_f<decltype(kind)::value>(dr, dc, s3, h.sv);
             }
+            });
             __syncthreads();
         }
+        with_prior_kind(v.prior_kind, [&](auto kind) {  // (the kind once per item, not per (cell, footprint cell) pair)
 #pragma unroll
         for (int c = 0; c < VEC; ++c) {
             const int cell = min(cell0 + c, v.N - 1);
@@ -230,13 +233,14 @@ __global__ __launch_bounds__(kMaxTileThreads, IPP_MINWAVES) void k_gain(View v, 
                 for (int a = 0; a < blk.count(); ++a) {
                     const int ly = blk.y0 + a / blk.bw, lx = blk.x0 + a % blk.bw;
                     const int dr = abs(row - (h.yu + ly)), dc = abs(col - (h.xl + lx));
-                    cb += use_lut ? lut[dr * v.W + dc] : matern_f(dr, dc, s3, h.sv);
+                    cb += use_lut ? lut[dr * v.W + dc] : prior_f<decltype(kind)::value>(dr, dc, s3, h.sv);
                 }
                 cb *= (float)blk.weight;
 #pragma unroll
                 for (int j = 0; j < MC; ++j) acc[c][j] = fmaf(cb, Ls[b * MC + j], acc[c][j]);
             }
         }
+        });
         if (use_lut) __syncthreads();  // the table is overwritten by Q below
     }
 

@@ -206,7 +206,7 @@ __device__ __forceinline__ void gain_tiles(const View& v, const ItemHdr& h, cons
     const int tid = threadIdx.x, T = blockDim.x;
     const int lane = tid & (kWave - 1), wave = tid / kWave, nw = NW > 0 ? NW : T / kWave;
     const int m = h.m, r = h.rank;
-    const float s3 = (float)(kSqrt3 * v.res) / h.ls;
+    const float s3 = prior_scale_f(v.prior_kind, v.res, h.ls);
     typedef const __attribute__((address_space(4))) float* cfloat_p;
     cfloat_p qrows_c = (cfloat_p)(const void*)qrows;
     if (QCONST) asm volatile("" : "+s"(qrows_c));  // defined here: no load through it can move above the caller's barrier
@@ -393,9 +393,10 @@ __device__ __forceinline__ void gain_tiles(const View& v, const ItemHdr& h, cons
             // The variants are chosen ONCE per tile (both wave-uniform): decided per lookup, every one of the up to 36 VEC
             // lookup sites carried a branch around ~25 instructions of inlined sqrt / exp code -- 144 taken branches per
             // tile and a 9 000-instruction tile body (54 KB: the instruction cache of a CU pair is 64 KB).
-            auto base_term = [&](auto lut_tag, auto nfc_tag) {
+            auto base_term = [&](auto lut_tag, auto nfc_tag, auto kind_tag) {
                 constexpr bool TL = decltype(lut_tag)::value;
                 constexpr int NFC = decltype(nfc_tag)::value;
+                constexpr int KIND = decltype(kind_tag)::value;
                 auto block_term = [&](int b, float (&cb)[VEC]) {
 #pragma unroll
                     for (int c = 0; c < VEC; ++c) cb[c] = 0.f;
@@ -410,7 +411,7 @@ __device__ __forceinline__ void gain_tiles(const View& v, const ItemHdr& h, cons
                             float p0;
                             // (24-bit multiply-add: v_mul_lo_u32 runs at quarter rate)
                             if constexpr (TL) p0 = lut[__umul24(dr, v.W) + dc];
-                            else p0 = matern_f(dr, dc, s3, h.sv);
+                            else p0 = prior_f<KIND>(dr, dc, s3, h.sv);
                             cb[c] = fmaf(wa, p0, cb[c]);
                         }
                     }
@@ -459,12 +460,15 @@ __device__ __forceinline__ void gain_tiles(const View& v, const ItemHdr& h, cons
             };
             typedef std::integral_constant<int, 1> one_cell_t;
             typedef std::integral_constant<int, 4> four_cells_t;
+            typedef std::integral_constant<int, IPP_PRIOR_MATERN32> table_kind_t;  // (the table holds the env's prior: no kind)
             if (tile_lut) {
-                if (h.rf == 1) base_term(std::true_type{}, one_cell_t{});
-                else base_term(std::true_type{}, four_cells_t{});
-            } else {  // (tall footprints / tables cut at 48 KiB only)
-                if (h.rf == 1) base_term(std::false_type{}, one_cell_t{});
-                else base_term(std::false_type{}, four_cells_t{});
+                if (h.rf == 1) base_term(std::true_type{}, one_cell_t{}, table_kind_t{});
+                else base_term(std::true_type{}, four_cells_t{}, table_kind_t{});
+            } else {  // (tall footprints / tables cut at 48 KiB only; the prior's kind chosen here, once per tile)
+                with_prior_kind(v.prior_kind, [&](auto kind) {
+                    if (h.rf == 1) base_term(std::false_type{}, one_cell_t{}, kind);
+                    else base_term(std::false_type{}, four_cells_t{}, kind);
+                });
             }
         }
 
@@ -774,11 +778,13 @@ __global__ __launch_bounds__(512, IPP_GF_MINWAVES) void k_gain_factor(View v, co
     }
     fill_block_tables<MC>(h, lds.fb_yx, lds.fb_w);
     {
-        const float s3 = (float)(kSqrt3 * v.res) / h.ls;
-        for (int i = tid; i < lut_rows * v.W; i += T) {
-            const int dr = i / v.W, dc = i - dr * v.W;
-            lds.lut[i] = matern_f(dr, dc, s3, h.sv);
-        }
+        const float s3 = prior_scale_f(v.prior_kind, v.res, h.ls);
+        with_prior_kind(v.prior_kind, [&](auto kind) {
+            for (int i = tid; i < lut_rows * v.W; i += T) {
+                const int dr = i / v.W, dc = i - dr * v.W;
+                lds.lut[i] = prior_f<decltype(kind)::value>(dr, dc, s3, h.sv);
+            }
+        });
     }
     __syncthreads();
     gain_tiles<MC, VEC, gf_pipe<MC, VEC>(), false, false, false, false, false, 0, RECT>(v, h, item, flags, lut_rows, lds, blk + LQ, reward_out);

@@ -72,7 +72,7 @@ __global__ __launch_bounds__(kWave, 4) void k_gain_wave(View v, const float* __r
     float* cov_dst = v.cov + (size_t)h.dst * v.cov_slot;
     const bool adaptive = (flags & IPP_ADAPTIVE) != 0;
     const size_t npad = (size_t)v.Npad;
-    const float s3 = (float)(kSqrt3 * v.res) / h.ls;
+    const float s3 = prior_scale_f(v.prior_kind, v.res, h.ls);
     double item_part = 0.0;
     unsigned long long units = 0;
 
@@ -104,10 +104,12 @@ __global__ __launch_bounds__(kWave, 4) void k_gain_wave(View v, const float* __r
         const int nlut = (dmax - dmin + 1) * v.W;
         const bool use_lut = nlut <= kTileLut;
         if (use_lut) {
+            with_prior_kind(v.prior_kind, [&](auto kind) {
             for (int i = lane; i < nlut; i += kWave) {
                 const int dr = i / v.W, dc = i - dr * v.W;
-                lut[i] = matern_f(dmin + dr, dc, s3, h.sv);
+                lut[i] = prior_f<decltype(kind)::value>(dmin + dr, dc, s3, h.sv);
             }
+            });
         }
         __syncthreads();  // single-wave workgroup: orders the LDS writes above before the reads below
 
@@ -127,6 +129,7 @@ __global__ __launch_bounds__(kWave, 4) void k_gain_wave(View v, const float* __r
             }
             // per block: 4 (padded, weight 0) footprint cells x VEC grid cells = 4*VEC independent table lookups in
             // flight, so the LDS latency is paid once per block instead of once per lookup
+            with_prior_kind(v.prior_kind, [&](auto kind) {  // (the kind once per tile, not per lookup)
             for (int b = 0; b < m; ++b) {
                 float cb[VEC];
 #pragma unroll
@@ -139,7 +142,7 @@ __global__ __launch_bounds__(kWave, 4) void k_gain_wave(View v, const float* __r
 #pragma unroll
                     for (int c = 0; c < VEC; ++c) {
                         const int dr = abs(crow[c] - fy), dc = abs(ccol[c] - fx);
-                        const float p0 = use_lut ? lut[(dr - dmin) * v.W + dc] : matern_f(dr, dc, s3, h.sv);
+                        const float p0 = use_lut ? lut[(dr - dmin) * v.W + dc] : prior_f<decltype(kind)::value>(dr, dc, s3, h.sv);
                         cb[c] = fmaf(wa, p0, cb[c]);
                     }
                 }
@@ -150,6 +153,7 @@ __global__ __launch_bounds__(kWave, 4) void k_gain_wave(View v, const float* __r
                     for (int c = 0; c < VEC; ++c) acc[c][j] = fmaf(cb[c], l, acc[c][j]);
                 }
             }
+            });
         }
 
         // ---- stream the stored rows: acc += row_k[cells] * Q[k,:]; Q row k is wave-uniform -> scalar loads

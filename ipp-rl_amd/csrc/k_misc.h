@@ -95,14 +95,16 @@ __global__ __launch_bounds__(256) void k_reset_dense(View v, const int* __restri
     for (int c = 0; c < 4; ++c) { cr[c] = (cell0 + c) / v.W; cc[c] = (cell0 + c) - cr[c] * v.W; }
     float* P = v.cov + (size_t)env * v.cov_slot;
     const int row0 = band * kBandRows, nrows = min(kBandRows, v.N - row0);
+    with_prior_kind(v.prior_kind, [&](auto kind) {
     for (int rr = 0; rr < nrows; ++rr) {
         const int i = row0 + rr, ri = i / v.W, ci = i - ri * v.W;
         float out[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c)
-            out[c] = (cell0 + c < v.N) ? (float)matern_d(ri - cr[c], ci - cc[c], v.res, sv, ls) : 0.f;
+            out[c] = (cell0 + c < v.N) ? (float)prior_d<decltype(kind)::value>(ri - cr[c], ci - cc[c], v.res, sv, ls) : 0.f;
         *reinterpret_cast<float4*>(P + (size_t)i * v.Npad + cell0) = make_float4(out[0], out[1], out[2], out[3]);
     }
+    });
 }
 
 // GRF as a circular convolution: field = white (*) h, h = Re ifft2(amp) (simulations/ground_truths.py:14-31;
@@ -249,7 +251,7 @@ __global__ __launch_bounds__(256) void k_read_cov_factor(View v, int env, float*
     if (i >= v.N || j >= v.N) return;
     const double sv = v.prior[2 * env + 0], ls = v.prior[2 * env + 1];
     const int ri = i / v.W, ci = i - ri * v.W, rj = j / v.W, cj = j - rj * v.W;
-    double acc = matern_d(ri - rj, ci - cj, v.res, sv, ls);
+    double acc = prior_d(v.prior_kind, ri - rj, ci - cj, v.res, sv, ls);
     const float* U = v.cov + (size_t)env * v.cov_slot;
     const int r = v.rank[env];
     const int ti = i / v.tile_cells, tj = j / v.tile_cells;

@@ -392,7 +392,7 @@ __device__ __forceinline__ ItemHdr* prepare_item_ex(const View& v, const int ite
             bcell[4 * tid + a] = (h.yu + ly) * v.W + h.xl + lx;
         }
     }
-    if (MODE == IPP_FACTOR && tid < f) ktab[tid] = matern_d(tid / h.w, tid % h.w, v.res, sv, ls);
+    if (MODE == IPP_FACTOR && tid < f) ktab[tid] = prior_d(v.prior_kind, tid / h.w, tid % h.w, v.res, sv, ls);
 #pragma unroll
     for (int q = 0; q < (FC + kPrepThreads - 1) / kPrepThreads; ++q) {
         const int fi = tid + q * kPrepThreads;

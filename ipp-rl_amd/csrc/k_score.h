@@ -183,6 +183,7 @@ __global__ __launch_bounds__(256) void k_score_densify(View v, ScoreView sv, int
         }
     }
     const double svv = v.prior[2 * env + 0], ls = v.prior[2 * env + 1];
+    with_prior_kind(v.prior_kind, [&](auto kind) {
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
         const int i = i0 + ti * 4 + a;
@@ -195,11 +196,12 @@ __global__ __launch_bounds__(256) void k_score_densify(View v, ScoreView sv, int
             float out = 0.f;
             if (j < v.N) {
                 const int rj = j / v.W, cj = j - rj * v.W;
-                out = (float)(matern_d(ri - rj, ci - cj, v.res, svv, ls) - (double)acc[a][b]);
+                out = (float)(prior_d<decltype(kind)::value>(ri - rj, ci - cj, v.res, svv, ls) - (double)acc[a][b]);
             }
             sv.P[(size_t)i * v.Npad + j] = out;
         }
     }
+    });
 }
 
 // ---------------------------------------------------------------- G band: G[i][j] = sum_k mask_k P[i][k] P[j][k]

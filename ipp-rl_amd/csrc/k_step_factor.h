@@ -98,11 +98,13 @@ __global__ __launch_bounds__(kStepThreads, IPP_GF_MINWAVES) void k_step_factor(
                 lds.mask4[q - q_lo] = (unsigned char)bits;
             }
         }
-        const float s3 = (float)(kSqrt3 * v.res) / hh.ls;
-        for (int i = tid; i < lut_rows * v.W; i += kStepThreads) {
-            const int dr = i / v.W, dc = i - dr * v.W;
-            lds.lut[i] = matern_f(dr, dc, s3, hh.sv);
-        }
+        const float s3 = prior_scale_f(v.prior_kind, v.res, hh.ls);
+        with_prior_kind(v.prior_kind, [&](auto kind) {
+            for (int i = tid; i < lut_rows * v.W; i += kStepThreads) {
+                const int dr = i / v.W, dc = i - dr * v.W;
+                lds.lut[i] = prior_f<decltype(kind)::value>(dr, dc, s3, hh.sv);
+            }
+        });
     };
     ItemHdr* hs = prepare_item_ex<MC, IPP_FACTOR, kStepThreads, true, decltype(mid), false, false, kDeferObs>(
         v, item, env_ids, nullptr, action, prev_action, meas_noise, flags, status_out, nullptr, nullptr, nullptr, lds.small,

@@ -481,14 +481,16 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_step_patch(
         if (any0) gather_issue(rc0, k0, on0, l0);
         // ---- under the round trip: prior table, footprint tables of the m x m algebra, the padding record
         {
-            const float s3 = (float)(kSqrt3 * v.res) / h.ls;
+            const float s3 = prior_scale_f(v.prior_kind, v.res, h.ls);
             const int lw = v.plw;
             float* lut_dst = SPLIT ? blk + SplitBlk::kTab + SplitBlk::kTabFixed : lds.lut;  // (split step: straight into the item's block)
-            for (int i = tid; i < lw * lw; i += NT) {
-                const int dr = div_small(i, lw), dc = i - dr * lw;
-                lut_dst[i] = matern_f(dr, dc, s3, h.sv);
-            }
-            if (ttid >= 0 && ttid < f) { const int ky = div_small(ttid, h.w); pl.ktab[ttid] = matern_d(ky, ttid - ky * h.w, v.res, sv_d, ls_d); }
+            with_prior_kind(v.prior_kind, [&](auto kind) {
+                for (int i = tid; i < lw * lw; i += NT) {
+                    const int dr = div_small(i, lw), dc = i - dr * lw;
+                    lut_dst[i] = prior_f<decltype(kind)::value>(dr, dc, s3, h.sv);
+                }
+            });
+            if (ttid >= 0 && ttid < f) { const int ky = div_small(ttid, h.w); pl.ktab[ttid] = prior_d(v.prior_kind, ky, ttid - ky * h.w, v.res, sv_d, ls_d); }
         }
         if (tid == 0) IPP_MARK(item, 5);
         if (any0) gather_store(rc0, k0, on0, lane, l0);
@@ -655,7 +657,7 @@ __global__ __launch_bounds__(256) void k_read_cov_patch(View v, int env, float* 
     if (i >= v.N || j >= v.N) return;
     const double sv = v.prior[2 * env + 0], ls = v.prior[2 * env + 1];
     const int ri = i / v.W, ci = i - ri * v.W, rj = j / v.W, cj = j - rj * v.W;
-    double acc = matern_d(ri - rj, ci - cj, v.res, sv, ls);
+    double acc = prior_d(v.prior_kind, ri - rj, ci - cj, v.res, sv, ls);
     const float* U = v.cov + (size_t)env * v.cov_slot;
     const int r = v.rank[env];
     for (int k = 0; k < r; ++k) {

@@ -121,11 +121,13 @@ __global__ __launch_bounds__(kStepThreads, IPP_GF_MINWAVES) void k_tree_step(
             for (int k = tid; k < hh.rank; k += kStepThreads) lds.stage_rect(k, cc.rect(k));
         // (mask and the new node's diagonal per tile, from the parent state's diagonal read under the tile's stream, like
         // k_tree_gain: the pass over the span in front of the stream was 9 of the 36 us of this prologue)
-        const float s3 = (float)(kSqrt3 * v.res) / hh.ls;
-        for (int i = tid; i < lut_rows * v.W; i += kStepThreads) {
-            const int dr = i / v.W, dc2 = i - dr * v.W;
-            lds.lut[i] = matern_f(dr, dc2, s3, hh.sv);
-        }
+        const float s3 = prior_scale_f(v.prior_kind, v.res, hh.ls);
+        with_prior_kind(v.prior_kind, [&](auto kind) {
+            for (int i = tid; i < lut_rows * v.W; i += kStepThreads) {
+                const int dr = i / v.W, dc2 = i - dr * v.W;
+                lds.lut[i] = prior_f<decltype(kind)::value>(dr, dc2, s3, hh.sv);
+            }
+        });
     };
     ItemHdr* hs = prepare_item_ex<MC, IPP_FACTOR, kStepThreads, true, decltype(mid), true>(
         v, item, root_ids, nullptr, action, prev_action, nullptr, flags_eff, status_out, nullptr, nullptr, nullptr, lds.small,
@@ -259,11 +261,13 @@ __global__ __launch_bounds__(512, IPP_GF_MINWAVES) void k_tree_gain(
     }
     fill_block_tables<MC>(h, lds.fb_yx, lds.fb_w);
     {
-        const float s3 = (float)(kSqrt3 * v.res) / h.ls;
-        for (int i = tid; i < lut_rows * v.W; i += T) {
-            const int dr = i / v.W, dc2 = i - dr * v.W;
-            lds.lut[i] = matern_f(dr, dc2, s3, h.sv);
-        }
+        const float s3 = prior_scale_f(v.prior_kind, v.res, h.ls);
+        with_prior_kind(v.prior_kind, [&](auto kind) {
+            for (int i = tid; i < lut_rows * v.W; i += T) {
+                const int dr = i / v.W, dc2 = i - dr * v.W;
+                lds.lut[i] = prior_f<decltype(kind)::value>(dr, dc2, s3, h.sv);
+            }
+        });
     }
     if (expand && tid == 0) { new_meta[2] = parent_id; new_meta[3] = root; }
     __syncthreads();

@@ -314,13 +314,15 @@ __global__ __launch_bounds__(64 * NW, kPatchMinW) void k_tree_patch(
         const long long off0 = col_off(on0 ? (int)klist[lane] : 0);
         if (any0) gather_issue(rc0, off0, on0, l0);
         {
-            const float s3 = (float)(kSqrt3 * v.res) / h.ls;
+            const float s3 = prior_scale_f(v.prior_kind, v.res, h.ls);
             const int lw = v.plw;
-            for (int i = tid; i < lw * lw; i += NT) {
-                const int dr = div_small(i, lw), dc = i - dr * lw;
-                lds.lut[i] = matern_f(dr, dc, s3, h.sv);
-            }
-            if (ttid >= 0 && ttid < f) { const int ky = div_small(ttid, h.w); pl.ktab[ttid] = matern_d(ky, ttid - ky * h.w, v.res, sv_d, ls_d); }
+            with_prior_kind(v.prior_kind, [&](auto kind) {
+                for (int i = tid; i < lw * lw; i += NT) {
+                    const int dr = div_small(i, lw), dc = i - dr * lw;
+                    lds.lut[i] = prior_f<decltype(kind)::value>(dr, dc, s3, h.sv);
+                }
+            });
+            if (ttid >= 0 && ttid < f) { const int ky = div_small(ttid, h.w); pl.ktab[ttid] = prior_d(v.prior_kind, ky, ttid - ky * h.w, v.res, sv_d, ls_d); }
         }
         if (tid == 0) IPP_MARK(item, 5);
         if (any0) gather_store(rc0, off0, on0, lane, l0);

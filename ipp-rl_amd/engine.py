@@ -38,6 +38,7 @@ class EngineConfig:
     value_threshold: float = 0.4
     interval_factor: float = 0.0
     cluster_radius: float = 5.0
+    nu: float = 1.5  # Matern smoothness of the GP prior (mapping.nu): 0.5, 1.5, 2.5 or inf (PRIOR_KINDS)
 
     @property
     def n_cells(self) -> int:
@@ -57,7 +58,27 @@ class EngineConfig:
             value_threshold=float(scen.get("value_threshold", 0.4)),
             interval_factor=float(scen.get("interval_factor", 0.0)),
             cluster_radius=float(sen.get("simulation", {}).get("cluster_radius", 5.0)),
+            nu=float(mp.get("nu", 1.5)),
         )
+
+
+# Matern nu -> the engine's prior kind (include/ipp_engine.h IPP_PRIOR_*): the values of nu that
+# sklearn.gaussian_process.kernels.Matern evaluates in closed form.  Any other nu needs Bessel functions.
+PRIOR_KINDS = {1.5: _ffi.IPP_PRIOR_MATERN32, 0.5: _ffi.IPP_PRIOR_MATERN12, 2.5: _ffi.IPP_PRIOR_MATERN52,
+               float("inf"): _ffi.IPP_PRIOR_RBF}
+PRIOR_NAMES = {_ffi.IPP_PRIOR_MATERN32: "matern32", _ffi.IPP_PRIOR_MATERN12: "matern12", _ffi.IPP_PRIOR_MATERN52: "matern52",
+               _ffi.IPP_PRIOR_RBF: "rbf"}
+
+
+def prior_kind(nu) -> int:
+    """IPP_PRIOR_* kind of the Matern prior with smoothness `nu`; ValueError for a nu the engine does not evaluate."""
+    try:
+        kind = PRIOR_KINDS.get(float(nu))
+    except (TypeError, ValueError):
+        kind = None
+    if kind is None:
+        raise ValueError(f"Matern nu = {nu!r} is not supported by the device prior: nu must be one of 0.5, 1.5, 2.5 or inf")
+    return kind
 
 
 def _torch():
@@ -188,7 +209,8 @@ class IPPEngine:
         DeviceArena of that kind owned by the engine; a DeviceArena instance = the caller's (the engine never frees it).
         window_rows: 0 = exact columns, R > 0 = columns kept within R grid rows of their footprint, -1 = the smallest
         R the engine accepts for this prior (ipp_min_window_rows).  fixed_prior: no reset will install a length scale above
-        cfg.length_scale (no shuffle_prior_cov), which lets the window be 10 instead of 12 rows for the example config."""
+        cfg.length_scale (no shuffle_prior_cov), which lets the window be 10 instead of 12 rows for the example config.
+        The prior is sigma^2 * Matern(l, cfg.nu) for nu in 0.5, 1.5, 2.5, inf (prior_kernel); other nu raise ValueError."""
         if _forked_with_gpu:
             raise _ffi.IppError(FORK_MESSAGE)
         torch = _torch()
@@ -196,6 +218,7 @@ class IPPEngine:
         if not torch.cuda.is_available():
             raise _ffi.IppError("IPPEngine needs a HIP device (torch.cuda.is_available() is False); there is no CPU fallback")
         self.cfg = cfg
+        self.prior_kind = prior_kind(getattr(cfg, "nu", 1.5))
         self.device = torch.device(device)
         self.capacity = int(capacity)
         self.state = state
@@ -223,13 +246,13 @@ class IPPEngine:
                 c.window_rows = 0
             else:
                 rows = C.c_int32(0)
-                _ffi.check(self._lib.ipp_min_window_rows(C.byref(c), C.byref(rows)))
+                _ffi.check(self._lib.ipp_min_window_rows_prior(C.byref(c), self.prior_kind, C.byref(rows)))
                 c.window_rows = int(rows.value)
         c.score_scratch = 1 if score_scratch else 0
         c.node_capacity = int(node_capacity)
         self._c = c
         nbytes = C.c_uint64(0)
-        _ffi.check(self._lib.ipp_engine_arena_bytes(C.byref(c), C.byref(nbytes)))
+        _ffi.check(self._lib.ipp_engine_arena_bytes_prior(C.byref(c), self.prior_kind, C.byref(nbytes)))
         dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
         # the arena: a torch tensor (default), or memory straight from the driver (DeviceArena: "hip" = hipMalloc, "vmm" = the
         # virtual-memory API) -- an arena the caching allocator has never seen, whose physical placement the caller can re-draw
@@ -275,7 +298,8 @@ class IPPEngine:
                 self.arena.fill_(0xFF)
         base = (self.arena.data_ptr() + 255) // 256 * 256
         handle = C.c_void_p()
-        _ffi.check(self._lib.ipp_engine_create(C.byref(c), dev_index, C.c_void_p(base), nbytes.value, C.byref(handle)))
+        _ffi.check(self._lib.ipp_engine_create_prior(C.byref(c), self.prior_kind, dev_index, C.c_void_p(base), nbytes.value,
+                                                     C.byref(handle)))
         self._h = handle
         _LIVE.add(self)
         info = _ffi.IppInfo()
@@ -283,6 +307,11 @@ class IPPEngine:
         self.info = info
         self.n_cells, self.n_pad, self.meas_cap = info.n_cells, info.n_pad, info.meas_cap
         self.rank_cap = int(rank_cap)
+
+    @property
+    def prior_kernel(self) -> str:
+        """The prior's covariance function: "matern12", "matern32", "matern52" or "rbf" (PRIOR_NAMES)."""
+        return PRIOR_NAMES[self.prior_kind]
 
     # ------------------------------------------------------------------ plumbing
     def close(self):

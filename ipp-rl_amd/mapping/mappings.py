@@ -6,8 +6,8 @@ kalman_filter_update) with the arithmetic on the GPU.
     IPP_GIVEN_OBSERVATION / IPP_COV_ONLY, out of place into a new state slot), fp32 state on the device; covariances
     are returned as DeviceCov (_device_array.py): array-likes that stay on the GPU until a caller looks at the whole
     matrix (results agree with the reference within 1e-5, tests/test_hip_classes.py).
-  * init_priors GP branch -> ipp_reset (analytic Matern-3/2 == the unfitted GPR the reference builds,
-    mapping/mappings.py:242-258); the shuffle_prior_cov draws stay on NumPy's legacy stream (:239-240).
+  * init_priors GP branch -> ipp_reset (analytic sigma^2 Matern(l, nu) for nu = 0.5, 1.5, 2.5, inf == the unfitted GPR
+    the reference builds, mapping/mappings.py:242-258); the shuffle_prior_cov draws stay on NumPy's legacy stream (:239-240).
   * the non-GP prior (:219-233) and the generic dense-H kalman_filter_update (:156-215, no caller in the
     reference) are plain library GEMMs: torch (rocBLAS) on the device.
 """
@@ -18,6 +18,7 @@ import numpy as np
 
 from .. import _runtime
 from .._device_array import DeviceCov
+from ..engine import prior_kind
 from .grid_maps import GridMap, _require
 
 logger = logging.getLogger(__name__)
@@ -46,7 +47,8 @@ class Mapping:
     # ---- engine plumbing (never pickled: looked up per call)
     def _engine(self):
         sv, ls = self._prior_scale if self._prior_scale is not None else (self.signal_variance, self.length_scale)
-        cfg = _runtime.engine_config_from(self.grid_map, self.sensor, self.signal_variance, self.length_scale)
+        nu = float(self.nu) if self.fit_gaussian_process else 1.5  # (_runtime.prior_nu: the simulation's engine is this one)
+        cfg = _runtime.engine_config_from(self.grid_map, self.sensor, self.signal_variance, self.length_scale, nu=nu)
         eng = _runtime.compat_engine(cfg)
         return eng, (sv, ls)
 
@@ -67,9 +69,11 @@ class Mapping:
             At = torch.as_tensor(A, dtype=torch.float64, device=eng.device)
             gm.cov_matrix = ((At @ At.T) / torch.linalg.norm(At, ord="fro")).cpu().numpy()
             return
-        if float(self.nu) != 1.5:
-            logger.error("Only the Matern nu=1.5 prior of config/example.yaml is implemented on the device")
-            raise ValueError
+        try:
+            prior_kind(self.nu)  # (before the shuffle draws: an unsupported nu consumes no random numbers)
+        except ValueError as exc:
+            logger.error(str(exc))
+            raise
         sv, ls = self.signal_variance, self.length_scale
         if self.shuffle_prior_cov:
             sv = np.random.uniform(low=0.8 * self.signal_variance, high=1.2 * self.signal_variance)

@@ -28,7 +28,7 @@ class ScalarFieldSimulation(Simulation):
         gm = self.sensor.grid_map
         mp = gm.params.get("mapping", {})
         cfg = _runtime.engine_config_from(gm, self.sensor, mp.get("signal_variance", 1.0), mp.get("length_scale", 1.0),
-                                          cluster_radius=self.cluster_radius)
+                                          cluster_radius=self.cluster_radius, nu=_runtime.prior_nu(mp))
         return _runtime.compat_engine(cfg)
 
     def create_ground_truth_map(self) -> np.array:

@@ -1,0 +1,311 @@
+"""
+GPU tests of the prior kinds (include/ipp_engine.h IPP_PRIOR_*: Matern nu = 0.5, 2.5 and inf next to the default 1.5) on every
+route a public default reaches: dense and shuffled resets, Mapping.update_grid_map (dense compat engine), exact and windowed
+factor engines (one launch, two groups on two queues, the split step), ipp_score_actions, ipp_tree_step and VecIPPEnv.
+References: the reference's priors and episodes for each nu (tests/golden/priors_nu.npz, gen_prior_golden.py) and the dense
+NumPy Kalman step of oracle/ipp_oracle.py started from the closed-form prior.  Tolerance 1e-5 (fp32 device state).
+"""
+import numpy as np
+import pytest
+
+from oracle import ipp_oracle as orc
+from tests.params import example_params
+from tests.test_prior_kernels_host import NUS, prior_matrix
+
+pytestmark = pytest.mark.gpu
+TOL = 1e-5
+UAV = {"max_v": 2.0, "max_a": 2.0}
+D = 6
+MIN_FIXED = {0.5: 14, 1.5: 10, 2.5: 8, float("inf"): 10}
+
+
+def host(t):
+    return t.detach().cpu().numpy().astype(np.float64)
+
+
+def cfg_of(nu, dim):
+    from ipp_rl_amd import EngineConfig
+
+    return EngineConfig(x_dim=dim, y_dim=dim, nu=nu)
+
+
+@pytest.mark.parametrize("prefix,nu", NUS)
+def test_dense_factor_and_shuffled_resets(golden, prefix, nu):
+    from ipp_rl_amd import IPPEngine
+
+    g = golden("priors_nu")
+    eng = IPPEngine(cfg_of(nu, 10), capacity=4, state="dense", rank_cap=1)
+    assert eng.prior_kernel == {0.5: "matern12", 2.5: "matern52"}.get(nu, "rbf")
+    eng.reset()
+    assert np.max(np.abs(host(eng.read_cov(0)) - g[prefix + "P0_10"])) < TOL
+    draws = g[prefix + "shuffle"]
+    eng.reset(prior_scale=draws[:, :2])
+    for k, row in enumerate(draws):
+        P = host(eng.read_cov(k))
+        assert np.max(np.abs(np.array([P[0, 0], P[0, 1], P[0, 11], P[5, 99]]) - row[2:])) < TOL
+    eng.close()
+    eng = IPPEngine(cfg_of(nu, 50), capacity=1, state="dense", rank_cap=1)
+    eng.reset()
+    P = host(eng.read_cov(0))
+    assert np.max(np.abs(P[[0, 1234, 2499]] - g[prefix + "P0_50_rows"])) < TOL
+    assert np.max(np.abs(np.diag(P) - g[prefix + "P0_50_diag"])) < TOL
+    eng.close()
+    for window_rows, dim in ((0, 10), (-1, 50)):  # factor state at rank 0: P0 through k_read_cov_factor / k_read_cov_patch
+        eng = IPPEngine(cfg_of(nu, dim), capacity=1, state="factor", rank_cap=64, window_rows=window_rows, fixed_prior=True)
+        eng.reset()
+        P = host(eng.read_cov(0))
+        want = g[prefix + "P0_10"] if dim == 10 else g[prefix + "P0_50_rows"]
+        assert np.max(np.abs((P if dim == 10 else P[[0, 1234, 2499]]) - want)) < TOL
+        eng.close()
+
+
+def build_classes(dim, nu, seed):
+    from ipp_rl_amd.mapping.grid_maps import GridMap
+    from ipp_rl_amd.mapping.mappings import Mapping
+    from ipp_rl_amd.sensors.cameras import RGBCamera
+    from ipp_rl_amd.sensors.models.sensor_models import AltitudeSensorModel
+    from ipp_rl_amd.simulations.simulations import GaussianRandomField
+
+    params = example_params(dim)
+    params["mapping"]["nu"] = nu
+    np.random.seed(seed)
+    gm = GridMap(params)
+    sensor = RGBCamera(params["sensor"]["field_of_view"], AltitudeSensorModel(0.05, 0.2), gm)
+    sim = GaussianRandomField(sensor, 5)
+    sensor.set_sensor_simulation(sim)
+    return gm, sensor, sim, Mapping(gm, sensor)
+
+
+@pytest.mark.parametrize("name", ["episode_rf1_20_s0", "episode_mixed_20_s4", "episode_rf1_50_s0"])
+@pytest.mark.parametrize("prefix,nu", NUS)
+def test_mapping_episodes(golden, prefix, nu, name):
+    """Mapping(params with mapping.nu) + simulate_prediction_step + update_grid_map over the reference's episodes."""
+    from ipp_rl_amd.planning.common.optimization import simulate_prediction_step
+
+    g15, g = golden(name), golden("priors_nu")
+    k = prefix + name + "_"
+    gm, sensor, sim, mapping = build_classes(g15["gt"].shape[0], nu, int(g15["seed"]))
+    prev = np.array([2.0, 2.0, 14.0])
+    for t, a in enumerate(g[k + "actions"]):
+        info = {"mean": gm.mean, "value_threshold": 0.4, "interval_factor": 0}
+        reward, _, _ = simulate_prediction_step(gm.cov_matrix, prev, a, mapping, UAV, info)
+        z = sensor.take_measurement(a, verbose=False)
+        m = int(g[k + "m"][t])
+        assert z.size == m and np.max(np.abs(z.ravel() - g[k + "z"][t][:m])) < TOL
+        mapping.update_grid_map(a, z)
+        assert abs(reward - g[k + "reward"][t]) < TOL, (t, reward, g[k + "reward"][t])
+        assert np.max(np.abs(gm.mean - g[k + "mean"][t])) < TOL
+        assert np.max(np.abs(np.diag(gm.cov_matrix) - g[k + "diag"][t])) < TOL
+        prev = a
+    P = np.asarray(gm.cov_matrix)
+    assert np.max(np.abs(P[g15["sample_rows"]] - g[k + "P_final_rows"])) < TOL
+    if k + "P_final_proj" in g.files:
+        # the whole final matrix: against the reference's through the fixture's probe vectors (an elementwise error of TOL
+        # moves P v by at most TOL |v|_1), and elementwise against the dense oracle's covariance chain from the closed form
+        V = np.random.RandomState(12345).standard_normal((P.shape[0], 4))
+        assert np.all(np.abs(P @ V - g[k + "P_final_proj"]) < TOL * np.abs(V).sum(axis=0))
+        dim = g15["gt"].shape[0]
+        ocfg = orc.OracleConfig(x_dim=dim, y_dim=dim)
+        P_or = prior_matrix(nu, dim)
+        for a in g[k + "actions"]:
+            _, P_or, _ = orc.update_grid_map(ocfg, P_or, None, a, cov_only=True)
+        assert np.max(np.abs(P - P_or)) < TOL
+
+
+def replay(eng, g15, g, k, env=0):
+    eng.reset(env_ids=[env], white_noise=g15["white"][None])
+    prev = np.array([2.0, 2.0, 14.0])
+    for t, a in enumerate(g15["actions"]):
+        reward, status = eng.step(a[None], prev[None], env_ids=[env], meas_noise=g15["eps"][t][None])
+        assert int(status[0]) == 0
+        assert abs(float(reward[0]) - g[k + "reward"][t]) < TOL, (t, float(reward[0]), g[k + "reward"][t])
+        assert np.max(np.abs(host(eng.read_mean(env)) - g[k + "mean"][t])) < TOL
+        assert np.max(np.abs(host(eng.read_diag(env)) - g[k + "diag"][t])) < TOL
+        prev = a
+    assert np.max(np.abs(host(eng.read_cov(env))[g15["sample_rows"]] - g[k + "P_final_rows"])) < TOL
+
+
+@pytest.mark.parametrize("window_rows,split", [(0, None), (-1, "0"), (-1, "1")])
+@pytest.mark.parametrize("prefix,nu", NUS)
+def test_factor_engines_replay_the_50x50_episode(golden, monkeypatch, prefix, nu, window_rows, split):
+    """Exact columns (k_gain_factor) and the smallest fixed-prior window of the kind (patch layout: the fused patch step, and
+    the split step under IPP_SPLIT=1) replay episode_rf1_50_s0 of that prior."""
+    from ipp_rl_amd import IPPEngine
+
+    name = "episode_rf1_50_s0"
+    g15, g = golden(name), golden("priors_nu")
+    if split is not None:
+        monkeypatch.setenv("IPP_SPLIT", split)  # read by ipp_engine_create
+    eng = IPPEngine(cfg_of(nu, 50), capacity=2, state="factor", rank_cap=360, window_rows=window_rows, fixed_prior=True)
+    if split is not None:
+        monkeypatch.delenv("IPP_SPLIT")
+    if window_rows < 0:
+        assert int(eng.info.window_rows) == MIN_FIXED[nu] and int(eng.info.patch_layout) == 1
+        assert int(eng.info.patch_split_min_items) == int(split)
+    replay(eng, g15, g, prefix + name + "_", env=1)
+    eng.close()
+
+
+@pytest.mark.parametrize("prefix,nu", NUS)
+def test_vec_env_two_parts_and_oracle_walk(prefix, nu):
+    """VecIPPEnv at the kind's smallest window: a few envs against the dense oracle from the closed-form prior; two groups on
+    two queues (parts=2) give the single launch's results bit for bit."""
+    import torch
+    from ipp_rl_amd.vec_env import VecIPPEnv, cell_centre_actions
+
+    cfg = cfg_of(nu, 50)
+    B = 256
+    env = VecIPPEnv(cfg, B, window_rows=-1, seed=3)
+    assert int(env.engine.info.patch_layout) == 1 and int(env.engine.info.window_rows) == MIN_FIXED[nu]
+    ocfg = orc.OracleConfig(x_dim=50, y_dim=50)
+    rs = np.random.RandomState(17)
+    white = rs.normal(size=(B, 50, 50))
+    env.reset(white_noise=white)
+    watch = (0, 77, B - 1)
+    states = {}
+    for b in watch:
+        states[b] = orc.env_reset(ocfg, white[b])
+        states[b].P = prior_matrix(nu, 50)
+    alts = [float(x) for x in range(5, 15)]
+    for t in range(4):
+        acts = cell_centre_actions(cfg, t, 0, B, B, alts)
+        eps = rs.normal(size=(B, 9))
+        reward, status = env.step(acts, meas_noise=eps, auto_reset=False)
+        torch.cuda.synchronize()
+        assert int(status.abs().sum()) == 0
+        for b in watch:
+            m = orc.num_measurements(orc.project_fov(ocfg, acts[b]), orc.resolution_factor(acts[b]))
+            out = orc.env_step(ocfg, states[b], acts[b], eps[b, :m])
+            assert abs(float(reward[b]) - out["reward"]) < TOL, (t, b, float(reward[b]), out["reward"])
+    for b in watch:
+        assert np.max(np.abs(host(env.mean(b)) - states[b].mean)) < TOL
+        assert np.max(np.abs(host(env.diag(b)) - np.diag(states[b].P))) < TOL
+    env.engine.close()
+
+    T = 4
+    one, two = (VecIPPEnv(cfg, B, episode_steps=T, stagger=True, window_rows=-1, seed=7, parts=p) for p in (1, 2))
+    assert two.parts == 2
+    one.reset()
+    two.reset()
+    for t in range(3 * T):
+        a = torch.as_tensor(cell_centre_actions(cfg, t, 0, B, B, alts), device="cuda")
+        r1, s1 = one.step(a)
+        two.step_async(a)
+    two.wait()
+    torch.cuda.synchronize()
+    assert torch.equal(r1, two.reward) and torch.equal(s1, two.status) and int(s1.abs().sum()) == 0
+    for e in (0, 1, B - 1):
+        assert torch.equal(one.mean(e), two.mean(e)) and torch.equal(one.diag(e), two.diag(e))
+    one.engine.close()
+    two.engine.close()
+
+
+def pad(path):
+    return list(path) + [-1] * (D - len(path))
+
+
+@pytest.mark.parametrize("dim", [50, 20])  # patch-layout tree kernels (k_tree_patch) / band tiles (k_tree: window >= 2R + 13 columns)
+@pytest.mark.parametrize("prefix,nu", NUS)
+def test_score_actions_and_tree_steps_vs_dense_oracle(prefix, nu, dim):
+    from ipp_rl_amd import IPPEngine
+
+    cfg = cfg_of(nu, dim)
+    ocfg = orc.OracleConfig(x_dim=dim, y_dim=dim)
+    eng = IPPEngine(cfg, capacity=3, state="factor", rank_cap=128, window_rows=-1, fixed_prior=True, node_capacity=32,
+                    max_batch=64, score_scratch=True)
+    assert int(eng.info.patch_layout) == (1 if dim == 50 else 0)
+    rs = np.random.RandomState(dim + 1)
+    white = rs.normal(size=(dim, dim))
+    eng.reset(env_ids=[2], white_noise=white[None])
+    st = orc.env_reset(ocfg, white)
+    st.P = prior_matrix(nu, dim)
+    prev = np.array([2.0, 2.0, 14.0])
+    centre = np.array([dim // 2, dim // 2])
+
+    def random_action():
+        c = np.clip(centre + rs.randint(-3, 4, size=2), 0, dim - 1)
+        return np.array([4.0 * c[0] + 2.0, 4.0 * c[1] + 2.0, float(rs.choice([6.0, 8.0, 12.0, 14.0]))])
+
+    for _ in range(4):  # a mid-episode root state
+        a = random_action()
+        eps = rs.normal(size=9)
+        eng.step(a[None], prev[None], env_ids=[2], meas_noise=eps[None])
+        m = orc.num_measurements(orc.project_fov(ocfg, a), orc.resolution_factor(a))
+        orc.env_step(ocfg, st, a, eps[:m])
+        prev = a
+    info = {"mean": st.mean, "value_threshold": 0.4, "interval_factor": 0.0}
+    cand = np.array([random_action() for _ in range(24)])
+    r_score, s_score = eng.score_actions(2, cand, prev)
+    assert int(s_score.abs().sum()) == 0
+    for k in range(len(cand)):
+        want = orc.predict_step(ocfg, st.P, prev, cand[k], UAV, info)[0]
+        assert abs(float(r_score[k]) - want) < TOL, (k, float(r_score[k]), want)
+    # a path of three recorded nodes, then predict-only queries from each of them
+    P_of, prev_of, path_of = {None: st.P}, {None: prev}, {None: []}
+    par = None
+    for nid in range(3):
+        a = random_action()
+        reward, status = eng.tree_step([2], [pad(path_of[par])], a[None], prev_of[par][None], new_ids=[nid])
+        assert int(status.abs().sum()) == 0
+        want, P_new, _, _ = orc.predict_step(ocfg, P_of[par], prev_of[par], a, UAV, info)
+        assert abs(float(reward[0]) - want) < TOL, (nid, float(reward[0]), want)
+        P_of[nid], prev_of[nid], path_of[nid] = P_new, a, path_of[par] + [nid]
+        par = nid
+    assert np.max(np.abs(host(eng.tree_diag(2)) - np.diag(P_of[2]))) < TOL
+    nodes = [None, 0, 1, 2]
+    acts = np.array([random_action() for _ in nodes])
+    prevs = np.array([prev_of[n] for n in nodes])
+    reward, status = eng.tree_step([2] * len(nodes), [pad(path_of[n]) for n in nodes], acts, prevs)
+    for k, n in enumerate(nodes):
+        assert abs(float(reward[k]) - orc.predict_step(ocfg, P_of[n], prevs[k], acts[k], UAV, info)[0]) < TOL
+    eng.close()
+
+
+@pytest.mark.parametrize("prefix,nu", NUS)
+def test_narrow_window_and_unsupported_nu_are_refused(prefix, nu):
+    from ipp_rl_amd import EngineConfig, IPPEngine
+    from ipp_rl_amd._ffi import IppError
+
+    rows = MIN_FIXED[nu]
+    with pytest.raises(IppError, match=f"window_rows >= {rows}"):
+        IPPEngine(cfg_of(nu, 50), capacity=1, state="factor", rank_cap=64, window_rows=rows - 1, fixed_prior=True)
+    with pytest.raises(ValueError, match="0.5, 1.5, 2.5 or inf"):
+        IPPEngine(EngineConfig(x_dim=20, y_dim=20, nu=1.0), capacity=1, state="factor", rank_cap=64)
+
+
+@pytest.mark.parametrize("dim,window_rows", [(50, -1), (20, 0)])
+def test_kind_0_through_the_prior_entries_is_bit_identical(golden, monkeypatch, dim, window_rows):
+    """The default prior (nu = 1.5) through ipp_engine_create_prior / _arena_bytes_prior / _min_window_rows_prior gives what the
+    old entry points give, bit for bit."""
+    from ipp_rl_amd import EngineConfig, IPPEngine, _ffi
+
+    lib = _ffi.load()
+    cfg = EngineConfig(x_dim=dim, y_dim=dim)
+    name = "episode_rf1_50_s0" if dim == 50 else "episode_rf1_20_s0"
+    g15 = golden(name)
+
+    def run(eng):
+        eng.reset(env_ids=[0], white_noise=g15["white"][None])
+        prev, rewards = np.array([2.0, 2.0, 14.0]), []
+        for t, a in enumerate(g15["actions"][:12]):
+            reward, _ = eng.step(a[None], prev[None], env_ids=[0], meas_noise=g15["eps"][t][None])
+            rewards.append(host(reward))
+            prev = a
+        out = (np.array(rewards), host(eng.read_mean(0)), host(eng.read_diag(0)), host(eng.read_cov(0)))
+        eng.close()
+        return out
+
+    new = IPPEngine(cfg, capacity=1, state="factor", rank_cap=360, window_rows=window_rows, fixed_prior=True)
+    assert new.prior_kind == _ffi.IPP_PRIOR_MATERN32 and new.prior_kernel == "matern32"
+    info_new = (int(new.info.window_rows), int(new.info.patch_layout))
+    a = run(new)
+    with monkeypatch.context() as mp:  # the same engine through the ABI-15 entry points
+        old_rows, old_bytes, old_create = lib.ipp_min_window_rows, lib.ipp_engine_arena_bytes, lib.ipp_engine_create
+        mp.setattr(lib, "ipp_min_window_rows_prior", lambda c, kind, rows: old_rows(c, rows), raising=True)
+        mp.setattr(lib, "ipp_engine_arena_bytes_prior", lambda c, kind, nb: old_bytes(c, nb), raising=True)
+        mp.setattr(lib, "ipp_engine_create_prior", lambda c, kind, *args: old_create(c, *args), raising=True)
+        old = IPPEngine(cfg, capacity=1, state="factor", rank_cap=360, window_rows=window_rows, fixed_prior=True)
+        assert (int(old.info.window_rows), int(old.info.patch_layout)) == info_new
+        b = run(old)
+    for x, y in zip(a, b):
+        assert np.array_equal(x, y)

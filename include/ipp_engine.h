@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define IPP_ABI_VERSION 16
+#define IPP_ABI_VERSION 17
 
 /* covariance state representation */
 #define IPP_DENSE  0 /* P[N][N] fp32 per env, updated in place (mapping/grid_maps.py:10-11)         */
@@ -39,6 +39,21 @@ extern "C" {
 #define IPP_PRIOR_MATERN12 1 /* nu = 0.5: exp(-d / l)                                         */
 #define IPP_PRIOR_MATERN52 2 /* nu = 2.5: (1 + t + t^2 / 3) exp(-t), t = sqrt(5) d / l         */
 #define IPP_PRIOR_RBF      3 /* nu = inf: exp(-d^2 / (2 l^2))                                  */
+
+/* ground-truth kinds (sensor.simulation.type, constants.py:74-89; simulations/simulation_factories.py:64-75) */
+#define IPP_FIELD_GRF     0 /* gaussian_random_field: min-max normalised Gaussian random field (ipp_generate_grf_*)  */
+#define IPP_FIELD_HOTSPOT 1 /* hotspot_random_field:  two clusters of `high` on `low` (simulations/simulations.py:50-90) */
+#define IPP_FIELD_SPLIT   2 /* split_random_field:    two levels split along y or x   (simulations/simulations.py:93-123) */
+
+/* A hotspot or split field: two values and up to two half-open rectangles {y0, y1, x0, x1} (y0 >= y1: empty).
+ * cell (y, x) = inside if it lies in rect[0] or rect[1], else outside; stored as (float)value.
+ *   hotspot: outside = low, inside = high, rect[0] / rect[1] = the first / second cluster
+ *   split:   outside = second, inside = first, rect[0] = [0, s) x [0, W) (y split) or [0, H) x [0, s) (x split), rect[1] empty */
+typedef struct ipp_field_record {
+    double  inside;
+    double  outside;
+    int32_t rect[2][4];
+} ipp_field_record;
 
 /* ipp_step flags */
 #define IPP_COV_ONLY        1u /* no observation / mean update     (mappings.py:114 cov_only=True)        */
@@ -468,6 +483,35 @@ int ipp_generate_grf_groups(void* engine, int32_t n, int32_t group_rows, const i
  * planning/mcts_zero/episode_generators.py:109-113 (a new episode's map, sampled when the previous one has run out of budget). */
 int ipp_generate_grf_refill(void* engine, int32_t n, const int32_t* refill /*[dev]*/, const int64_t* episode /*[dev] int64[capacity]*/,
                             int64_t row_offset, uint64_t seed, uint64_t subsequence, void* stream);
+
+/*
+ * Ground truths of kind IPP_FIELD_* drawn on the device, with the arguments and destinations of ipp_generate_grf_groups /
+ * ipp_generate_grf_refill.  IPP_FIELD_GRF forwards to those calls (their grids, -3 elsewhere).  IPP_FIELD_HOTSPOT / IPP_FIELD_SPLIT run
+ * on every grid the engine accepts, with the config's cluster_radius; they draw no white noise.  Field i takes the Philox4x32-10
+ * uniforms u_k = (word 0 + 0.5) / 2^32 of counter (row id) * 8 + k, row id = (row_ids ? row_ids[i] : i) + row_offset, under the key
+ * seed and the subsequence of the GRF call, and maps them in the reference's draw order:
+ *   value = a + (b - a) u;  randint(lo, hi) = lo + min(floor(u (hi - lo)), hi - lo - 1);  rand() > 0.5 = u > 0.5
+ *   hotspot (simulations/simulations.py:56-90): u0 high ~ U(0.7, 1), u1 low ~ U(0, 0.3), u2 / u3 the first centre (yc, xc) ~
+ *     randint(trunc(r), H / W); u4 / u5 the second centre, uniform over {c in [trunc(r), H) : |c - yc| > r} x (the same in x) -- the
+ *     distribution of the reference's rejection loop (:71-86) without the loop.  Cluster bounds int(max(c - r, 0)) .. int(min(c + r, H)).
+ *     Returns -1 where such a set can be empty (the reference would loop forever) and for r < 0 or trunc(r) >= H / W.
+ *   split (:99-123): u0 high ~ U(0.65, 1), u1 low ~ U(0, 0.35), u2 > 0.5 swaps first / second, u3 > 0.5 splits along y at
+ *     s ~ randint(ceil(0.33 H), ceil(0.66 H) + 1), else along x at s ~ randint(floor(0.33 W), ceil(0.66 W) + 1).
+ * A fill launch is store-bound: one workgroup per field, the record computed once, the plane written with 16-byte stores.
+ */
+int ipp_generate_field_groups(void* engine, int32_t kind, int32_t n, int32_t group_rows, const int64_t* group_subsequence /*[host] or NULL*/,
+                              const int32_t* row_ids /*[dev] or NULL*/, int64_t row_offset, uint64_t seed, uint64_t subsequence,
+                              float* gt_out /*[dev]*/, void* stream);
+/* ... the refill form of a budget step (ipp_generate_grf_refill): field i into the ALTERNATE plane of env refill[i] (negative: skipped),
+ * drawn from subsequence + episode[env] + 1; sets the env's staged flag.  planning/mcts_zero/episode_generators.py:109-113. */
+int ipp_generate_field_refill(void* engine, int32_t kind, int32_t n, const int32_t* refill /*[dev]*/, const int64_t* episode /*[dev]*/,
+                              int64_t row_offset, uint64_t seed, uint64_t subsequence, void* stream);
+/* Caller-given records (e.g. drawn on the host from NumPy's stream like HotspotRandomField / SplitRandomField,
+ * simulations/simulations.py:50-123): field i = records[i] into gt_out [n][H][W], or with gt_out == NULL into the ALTERNATE plane of
+ * env row_ids[i] (negative: skipped; sets its staged flag, the next folded reset flips to it).  Rectangles are clipped to the grid.
+ *   records [dev] ipp_field_record[n] */
+int ipp_fill_fields(void* engine, int32_t n, const ipp_field_record* records /*[dev]*/, const int32_t* row_ids /*[dev] or NULL*/,
+                    float* gt_out /*[dev]*/, void* stream);
 
 /*
  * One fused environment step for `n` items.  Replaces, per item:

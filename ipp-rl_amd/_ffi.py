@@ -15,10 +15,11 @@ IPP_PRIOR_MATERN32, IPP_PRIOR_MATERN12, IPP_PRIOR_MATERN52, IPP_PRIOR_RBF = 0, 1
 IPP_COV_ONLY, IPP_PREDICT_ONLY, IPP_ADAPTIVE, IPP_USE_FLIGHT_TIME, IPP_GIVEN_OBSERVATION, IPP_UPDATE_PREV = 1, 2, 4, 8, 16, 32
 IPP_BUDGET, IPP_RESET_ON_DONE = 64, 128
 IPP_BUDGET_STREAM = 3 << 40
+IPP_FIELD_GRF, IPP_FIELD_HOTSPOT, IPP_FIELD_SPLIT = 0, 1, 2
 STATUS_OK, STATUS_CHOL_FALLBACK, STATUS_NOT_PD, STATUS_RANK_FULL, STATUS_BAD_FOOTPRINT = 0, 1, 2, 3, 4
 IPP_MAX_MEAS = 25
-ABI_VERSION = 16
-AB_MIN_ABI = 13  # oldest library tools/ab_kernels.py may load under IPP_AB_OLD_LIB (v14 added the ipp_arena_* calls, v15 the budget ledger calls, v16 the *_prior calls; nothing else)
+ABI_VERSION = 17
+AB_MIN_ABI = 13  # oldest library tools/ab_kernels.py may load under IPP_AB_OLD_LIB (v14 added the ipp_arena_* calls, v15 the budget ledger calls, v16 the *_prior calls, v17 the field calls; nothing else)
 IPP_ARENA_HIPMALLOC, IPP_ARENA_VMM = 0, 1
 
 
@@ -46,6 +47,11 @@ class IppInfo(C.Structure):
         ("fused_step", C.c_int32), ("patch_layout", C.c_int32), ("patch_waves", C.c_int32), ("patch_big_min_items", C.c_int32),
         ("patch_split_min_items", C.c_int32), ("patch_two_wave_min_items", C.c_int32),
     ]
+
+
+class IppFieldRecord(C.Structure):
+    """ipp_field_record: cell (y, x) = inside if it lies in rect[0] or rect[1] ({y0, y1, x0, x1}, half-open), else outside."""
+    _fields_ = [("inside", C.c_double), ("outside", C.c_double), ("rect", (C.c_int32 * 4) * 2)]
 
 
 class IppStepItem(C.Structure):
@@ -117,6 +123,9 @@ PROTOTYPES = {
     "ipp_generate_grf_rows": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_uint64, C.c_uint64, _P, _P]),
     "ipp_generate_grf_groups": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, C.c_int64, C.c_uint64, C.c_uint64, _P, _P]),
     "ipp_generate_grf_refill": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int64, C.c_uint64, C.c_uint64, _P]),
+    "ipp_generate_field_groups": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int64, C.c_uint64, C.c_uint64, _P, _P]),
+    "ipp_generate_field_refill": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, C.c_int64, C.c_uint64, C.c_uint64, _P]),
+    "ipp_fill_fields": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
     "ipp_set_budget": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_double, C.c_int32, C.c_int32, C.c_uint64, C.c_int64]),
     "ipp_step": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, C.c_uint32, _P, _P, _P]),
     "ipp_step_autoreset": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P]),

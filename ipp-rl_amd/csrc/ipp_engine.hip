@@ -24,6 +24,7 @@
 #include "k_grf_dft.h"
 #include "k_grf_hartley.h"
 #include "k_grf_fft.h"
+#include "k_fields.h"
 #include "k_score.h"
 #include "k_plane.h"
 #include "k_tree.h"
@@ -1394,6 +1395,94 @@ int ipp_generate_grf_refill(void* engine, int32_t n, const int32_t* refill, cons
     HIP_TRY(hipSetDevice(e->device));
     GrfNoise gn = {refill, (long long)row_offset, seed, subsequence, 0, {0}, 1, reinterpret_cast<const long long*>(episode)};
     return launch_grf(e, n, nullptr, e->v.grf_raw2, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream), &gn);
+}
+
+}  // extern "C"
+
+namespace {
+
+// Hotspot draws need a non-empty set of admissible second centres for every first centre on both axes (the reference's rejection
+// loop, simulations/simulations.py:71-86, never ends otherwise) and trunc(r) < dim (its randint raises).
+bool hotspot_axis_ok(int dim, double r) {
+    if (!(r >= 0.0) || (double)(int)std::min(r, 1e9) >= (double)dim) return false;
+    const int lo = (int)r;
+    for (int c = lo; c < dim; ++c) {
+        const int left_end = (int)std::ceil((double)c - r) - 1, right_beg = (int)std::floor((double)c + r) + 1;
+        if (std::max(0, left_end - lo + 1) + std::max(0, dim - std::max(right_beg, lo)) == 0) return false;
+    }
+    return true;
+}
+
+int field_kind_check(const Engine* e, int kind, const char* fn) {
+    if (kind == IPP_FIELD_HOTSPOT) {
+        const double r = e->cfg.cluster_radius;
+        if (!hotspot_axis_ok(e->v.H, r) || !hotspot_axis_ok(e->v.W, r))
+            return fail(-1, "%s: hotspot fields on %d x %d with cluster_radius %g: a first centre can leave no second one more than r away "
+                            "on an axis (the reference loops forever), or trunc(r) >= the grid", fn, e->v.H, e->v.W, r);
+        return 0;
+    }
+    if (kind == IPP_FIELD_SPLIT) return 0;
+    return fail(-1, "%s: unknown field kind %d", fn, kind);
+}
+
+int launch_fields(Engine* e, int n, int kind, const ipp_field_record* rec, float* gt_out, const GrfNoise& gn, hipStream_t s) {
+    const View& v = e->v;
+    const bool vec4 = gt_out ? ((v.N & 3) == 0 && (reinterpret_cast<uintptr_t>(gt_out) & 15) == 0)
+                             : ((v.Npad & 3) == 0 && (reinterpret_cast<uintptr_t>(v.gt) & 15) == 0);
+    if (gn.episode)
+        hipLaunchKernelGGL((k_fields<true>), dim3(n), dim3(kFieldThreads), 0, s, v, n, kind, e->cfg.cluster_radius, rec, gt_out, gn, (int)vec4);
+    else
+        hipLaunchKernelGGL((k_fields<false>), dim3(n), dim3(kFieldThreads), 0, s, v, n, kind, e->cfg.cluster_radius, rec, gt_out, gn, (int)vec4);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ipp_generate_field_groups(void* engine, int32_t kind, int32_t n, int32_t group_rows, const int64_t* group_subsequence, const int32_t* row_ids,
+                              int64_t row_offset, uint64_t seed, uint64_t subsequence, float* gt_out, void* stream) {
+    if (kind == IPP_FIELD_GRF)
+        return ipp_generate_grf_groups(engine, n, group_rows, group_subsequence, row_ids, row_offset, seed, subsequence, gt_out, stream);
+    Engine* e = as_engine(engine);
+    if (!e) return fail(-1, "null engine");
+    if (int rc = field_kind_check(e, kind, "ipp_generate_field_groups")) return rc;
+    if (!gt_out && !row_ids) return fail(-1, "ipp_generate_field_groups: gt_out == NULL writes the alternate plane of env row_ids[i]: row_ids needed");
+    if (n < 0 || n > e->v.max_batch) return fail(-1, "n = %d outside [0, max_batch = %d]", n, e->v.max_batch);
+    if (n == 0) return 0;
+    if (group_rows < 0 || (group_rows > 0 && (!group_subsequence || (n + group_rows - 1) / group_rows > 16)))
+        return fail(-1, "ipp_generate_field_groups: at most 16 groups of group_rows fields, with their subsequence offsets");
+    HIP_TRY(hipSetDevice(e->device));
+    GrfNoise gn = {row_ids, (long long)row_offset, seed, subsequence, group_rows, {0}, gt_out ? 0 : 1};
+    for (int g = 0; group_rows > 0 && g < (n + group_rows - 1) / group_rows; ++g) gn.group_subseq[g] = (long long)group_subsequence[g];
+    return launch_fields(e, n, kind, nullptr, gt_out, gn, reinterpret_cast<hipStream_t>(stream));
+}
+
+int ipp_generate_field_refill(void* engine, int32_t kind, int32_t n, const int32_t* refill, const int64_t* episode, int64_t row_offset,
+                              uint64_t seed, uint64_t subsequence, void* stream) {
+    if (kind == IPP_FIELD_GRF) return ipp_generate_grf_refill(engine, n, refill, episode, row_offset, seed, subsequence, stream);
+    Engine* e = as_engine(engine);
+    if (!e) return fail(-1, "null engine");
+    if (int rc = field_kind_check(e, kind, "ipp_generate_field_refill")) return rc;
+    if (!refill || !episode) return fail(-1, "ipp_generate_field_refill: refill and episode are required");
+    if (n < 0 || n > e->v.max_batch) return fail(-1, "n = %d outside [0, max_batch = %d]", n, e->v.max_batch);
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(e->device));
+    GrfNoise gn = {refill, (long long)row_offset, seed, subsequence, 0, {0}, 1, reinterpret_cast<const long long*>(episode)};
+    return launch_fields(e, n, kind, nullptr, nullptr, gn, reinterpret_cast<hipStream_t>(stream));
+}
+
+int ipp_fill_fields(void* engine, int32_t n, const ipp_field_record* records, const int32_t* row_ids, float* gt_out, void* stream) {
+    Engine* e = as_engine(engine);
+    if (!e) return fail(-1, "null engine");
+    if (!records) return fail(-1, "ipp_fill_fields: records are required");
+    if (!gt_out && !row_ids) return fail(-1, "ipp_fill_fields: gt_out == NULL writes the alternate plane of env row_ids[i]: row_ids needed");
+    if (n < 0 || n > e->v.max_batch) return fail(-1, "n = %d outside [0, max_batch = %d]", n, e->v.max_batch);
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(e->device));
+    GrfNoise gn = {gt_out ? nullptr : row_ids, 0, 0, 0, 0, {0}, gt_out ? 0 : 1};
+    return launch_fields(e, n, IPP_FIELD_HOTSPOT, records, gt_out, gn, reinterpret_cast<hipStream_t>(stream));
 }
 
 int ipp_observe(void* engine, const int32_t* env_ids, int32_t n, const double* action, const float* meas_noise,

@@ -39,6 +39,8 @@ class EngineConfig:
     interval_factor: float = 0.0
     cluster_radius: float = 5.0
     nu: float = 1.5  # Matern smoothness of the GP prior (mapping.nu): 0.5, 1.5, 2.5 or inf (PRIOR_KINDS)
+    # ground truths (sensor.simulation.type): gaussian_random_field, hotspot_random_field or split_random_field (fields.KINDS)
+    simulation: str = "gaussian_random_field"
 
     @property
     def n_cells(self) -> int:
@@ -59,6 +61,7 @@ class EngineConfig:
             interval_factor=float(scen.get("interval_factor", 0.0)),
             cluster_radius=float(sen.get("simulation", {}).get("cluster_radius", 5.0)),
             nu=float(mp.get("nu", 1.5)),
+            simulation=str(sen.get("simulation", {}).get("type", "gaussian_random_field")),
         )
 
 
@@ -489,6 +492,62 @@ class IPPEngine:
         _ffi.check(rc)
         self._keep_grf = ids
         return True
+
+    def generate_fields_rows(self, kind: int, n: int, seed: int, subsequence: int, out, row_ids=None, row_offset: int = 0, stream=None,
+                             group_rows: int = 0, group_subsequence=None) -> bool:
+        """generate_grf_rows for ground truths of kind IPP_FIELD_* (ipp_generate_field_groups): same arguments, keying and destinations
+        (out=None: the alternate planes of env slots row_ids).  Hotspot / split fields run on every grid; False only for GRF on a grid
+        whose generator does not draw its own noise."""
+        torch = _torch()
+        ids = self._dev(row_ids, torch.int32)
+        st = self.stream if stream is None else C.c_void_p(stream.cuda_stream)
+        gs = None
+        if group_rows:
+            gs = (C.c_int64 * len(group_subsequence))(*[int(x) for x in group_subsequence])
+        rc = self._lib.ipp_generate_field_groups(self._h, int(kind), int(n), int(group_rows), gs, self._ptr(ids), int(row_offset),
+                                                 int(seed) & (2 ** 64 - 1), int(subsequence) & (2 ** 64 - 1), self._ptr(out), st)
+        if rc == -3:
+            return False
+        _ffi.check(rc)
+        self._keep_fields = ids
+        return True
+
+    def generate_fields_refill(self, kind: int, n: int, refill, episode, seed: int, subsequence: int, row_offset: int = 0,
+                               stream=None) -> bool:
+        """generate_grf_refill for ground truths of kind IPP_FIELD_* (ipp_generate_field_refill)."""
+        st = self.stream if stream is None else C.c_void_p(stream.cuda_stream)
+        rc = self._lib.ipp_generate_field_refill(self._h, int(kind), int(n), self._ptr(refill), self._ptr(episode), int(row_offset),
+                                                 int(seed) & (2 ** 64 - 1), int(subsequence) & (2 ** 64 - 1), st)
+        if rc == -3:
+            return False
+        _ffi.check(rc)
+        return True
+
+    def fill_fields(self, records, row_ids=None, out=None, stream=None):
+        """ipp_fill_fields: records (fields.RECORD_DTYPE array [n], or a device uint8 tensor of n x 48 bytes) -> fields into `out`
+        [n, N] (a new tensor when out is None and row_ids is None), or with out=None and row_ids into the alternate planes of those
+        env slots.  Returns out."""
+        torch = _torch()
+        from .fields import RECORD_DTYPE
+
+        if isinstance(records, torch.Tensor):
+            rec = records.to(device=self.device).contiguous()
+            n = rec.numel() // RECORD_DTYPE.itemsize
+        else:
+            arr = np.ascontiguousarray(np.asarray(records, dtype=RECORD_DTYPE).reshape(-1))
+            n = len(arr)
+            rec = torch.from_numpy(arr.view(np.uint8).copy()).to(self.device)
+        ids = self._dev(row_ids, torch.int32)
+        if out is None and ids is None:
+            out = torch.empty((n, self.n_cells), dtype=torch.float32, device=self.device)
+        if out is not None and (out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < n * self.n_cells):
+            raise ValueError(f"fill_fields: out must be a contiguous float32 device tensor of at least {n} x {self.n_cells} cells")
+        if ids is not None and ids.numel() < n:
+            raise ValueError("fill_fields: one row id per record")
+        st = self.stream if stream is None else C.c_void_p(stream.cuda_stream)
+        _ffi.check(self._lib.ipp_fill_fields(self._h, int(n), self._ptr(rec), self._ptr(ids), self._ptr(out), st))
+        self._keep_fill = (rec, ids)
+        return out
 
     def step(self, actions, prev_actions, env_ids=None, dst_ids=None, meas_noise=None, *, cov_only=False,
              predict_only=False, adaptive=True, use_flight_time=True, given_observation=False, reward_out=None,

@@ -5,8 +5,10 @@ take_measurement: the standard normals come from NumPy's legacy global stream (o
 measurement, like sensor_manipulations.py:56-57, so seeded runs consume the stream identically); crop,
 INTER_AREA downsample, scaling by the noise "variance", add and clip run in the HIP prologue kernel
 (ipp_observe).  create_ground_truth_map: white noise from the same stream, FFT-filtered field on the device
-(ipp_reset).  Hotspot / Split / Temperature generators of the reference are host-side dataset generators
-outside the hot path and are not provided.
+(ipp_reset).  HotspotRandomField / SplitRandomField (reference :50-123): the reference's own NumPy calls on the legacy stream, in its
+order (the hotspot's rejection loop included), build the field's record (two values, at most two rectangles: ipp_rl_amd.fields) and
+ipp_fill_fields writes the map on the device.  TemperatureDataField is not provided: it needs a dataset the reference does not ship,
+plus imageio and cv2.
 """
 import logging
 import math
@@ -14,7 +16,7 @@ import math
 import numpy as np
 
 from . import Simulation
-from .. import _runtime
+from .. import _runtime, fields
 
 logger = logging.getLogger(__name__)
 
@@ -66,3 +68,33 @@ class GaussianRandomField(ScalarFieldSimulation):
         eng = self._engine()
         eng.reset(env_ids=[1], white_noise=white[None])
         return _runtime.to_host64(eng.read_gt(1))
+
+
+class HotspotRandomField(ScalarFieldSimulation):
+    def __init__(self, sensor, cluster_radius: float):
+        super().__init__(sensor, cluster_radius)
+        self.ground_truth_map = self.create_ground_truth_map()
+
+    def create_ground_truth_map(self) -> np.array:
+        """Two clusters of `high` on `low` (reference :56-90).  ValueError where the reference's loop would never end."""
+        gm = self.sensor.grid_map
+        rec = fields.hotspot_record_numpy(gm.y_dim, gm.x_dim, self.cluster_radius)
+        return _fill_record(self, rec)
+
+
+class SplitRandomField(ScalarFieldSimulation):
+    def __init__(self, sensor, cluster_radius: float):
+        super().__init__(sensor, cluster_radius)
+        self.ground_truth_map = self.create_ground_truth_map()
+
+    def create_ground_truth_map(self) -> np.array:
+        """Two levels split along y or x (reference :99-123)."""
+        gm = self.sensor.grid_map
+        rec = fields.split_record_numpy(gm.y_dim, gm.x_dim)
+        return _fill_record(self, rec)
+
+
+def _fill_record(sim: ScalarFieldSimulation, rec) -> np.array:
+    gm = sim.sensor.grid_map
+    out = sim._engine().fill_fields(np.asarray(rec).reshape(1))
+    return _runtime.to_host64(out[0]).reshape(gm.y_dim, gm.x_dim)

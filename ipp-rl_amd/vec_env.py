@@ -5,7 +5,8 @@ slots on one GPU.
 One env step = the reference's self-play step sequence fused (planning/mcts_zero/episode_generators.py:
 137-146): simulate_prediction_step (reward) + sensor.take_measurement + mapping.update_grid_map.
 Episodes are ``episode_steps`` long (max_episode_steps, config/example.yaml:64); an episode reset draws a
-new Gaussian-random-field ground truth and (optionally) shuffled prior hyper-parameters
+new ground truth of the config's kind (cfg.simulation: Gaussian random field, hotspot or split field) and (optionally) shuffled
+prior hyper-parameters
 (shuffle_prior_cov, mapping/mappings.py:238-240) and returns the UAV to Mission.init_action
 (planning/missions.py:69).
 
@@ -25,6 +26,7 @@ import numpy as np
 
 from . import _ffi
 from .engine import EngineConfig, IPPEngine
+from .fields import check_hotspot, field_kind
 
 INIT_ACTION = (2.0, 2.0, 14.0)  # planning/missions.py:69
 
@@ -109,12 +111,16 @@ class VecIPPEnv:
         self.adaptive, self.use_flight_time = adaptive, use_flight_time
         self.budget_mode = budget is not None
         self.initial_budget, self.shuffle_budget = (float(budget) if budget is not None else None), bool(shuffle_budget)
+        # ground-truth kind (sensor.simulation.type): hotspot / split fields are drawn on the device on every grid (fields.py)
+        self.field_kind = field_kind(cfg.simulation)
+        if self.field_kind == _ffi.IPP_FIELD_HOTSPOT:
+            check_hotspot(cfg.y_dim, cfg.x_dim, cfg.cluster_radius)
         if self.budget_mode:
             if shuffle_prior_cov:
                 raise ValueError("budget mode: per-episode shuffled priors are not supported (shuffle_prior_cov)")
             if state != "factor":
                 raise ValueError("budget mode: patch-layout factor engines only (state='factor')")
-            if cfg.x_dim != cfg.y_dim or cfg.x_dim not in (50, 100):
+            if self.field_kind == _ffi.IPP_FIELD_GRF and (cfg.x_dim != cfg.y_dim or cfg.x_dim not in (50, 100)):
                 raise ValueError("budget mode: grids whose ground-truth generator draws its own noise only (50x50, 100x100)")
             if not (self.initial_budget >= cfg.resolution):
                 raise ValueError(f"budget mode: budget {budget} below the grid resolution {cfg.resolution}")
@@ -300,10 +306,16 @@ class VecIPPEnv:
             sel = np.nonzero(epi == e)[0].astype(np.int32)
             ids = torch.as_tensor(sel, device=self.device)
             white = self._white[:len(sel)]
-            self.engine.normal_rows(white, self.cfg.n_cells, self.seed, self.GT_STREAM + int(e), row_ids=ids, row_offset=self.env_id_offset)
-            self.engine.reset(env_ids=ids, white_noise=white, prev=self.prev, init_action=INIT_ACTION)
+            if self.field_kind == _ffi.IPP_FIELD_GRF:
+                self.engine.normal_rows(white, self.cfg.n_cells, self.seed, self.GT_STREAM + int(e), row_ids=ids, row_offset=self.env_id_offset)
+                self.engine.reset(env_ids=ids, white_noise=white, prev=self.prev, init_action=INIT_ACTION)
+            else:
+                self.engine.generate_fields_rows(self.field_kind, len(sel), self.seed, self.GT_STREAM + int(e), white, row_ids=ids,
+                                                 row_offset=self.env_id_offset)
+                self.engine.reset(env_ids=ids, gt=white, prev=self.prev, init_action=INIT_ACTION)
             # the next episode's field into the alternate planes: a reset on done flips to it
-            self.engine.generate_grf_rows(len(sel), self.seed, self.GT_STREAM + int(e) + 1, None, row_ids=ids, row_offset=self.env_id_offset)
+            self.engine.generate_fields_rows(self.field_kind, len(sel), self.seed, self.GT_STREAM + int(e) + 1, None, row_ids=ids,
+                                             row_offset=self.env_id_offset)
         self.episode.copy_(torch.as_tensor(epi, device=self.device))
         self.budget.copy_(torch.as_tensor(start_budget(self.initial_budget, self.shuffle_budget, self.seed, gid, epi), device=self.device))
         self.depth.copy_(self.phase.to(torch.int32))
@@ -321,7 +333,8 @@ class VecIPPEnv:
                          reward_out=self.reward, status_out=self.status, update_prev=True, budget=True, reset_on_done=auto_reset,
                          init_action=INIT_ACTION)
         if auto_reset:
-            self.engine.generate_grf_refill(self.num_envs, self.refill, self.episode, self.seed, self.GT_STREAM, row_offset=self.env_id_offset)
+            self.engine.generate_fields_refill(self.field_kind, self.num_envs, self.refill, self.episode, self.seed, self.GT_STREAM,
+                                               row_offset=self.env_id_offset)
         self.t += 1
         return self.reward, self.status
 
@@ -392,7 +405,10 @@ class VecIPPEnv:
         if n == 0:
             return
         if gt is None and white_noise is None:
-            white_noise = self._white_for(ids, self._ids_host(ids, env_ids, _phase), self._white[:n])
+            if self.field_kind == _ffi.IPP_FIELD_GRF:
+                white_noise = self._white_for(ids, self._ids_host(ids, env_ids, _phase), self._white[:n])
+            else:
+                gt = self._fields_for(ids, self._ids_host(ids, env_ids, _phase), self._white[:n])
         if prior_scale is None and self.shuffle_prior_cov:
             if _phase is not None:
                 prior_scale = self._prior_scale_scheduled(_phase)
@@ -473,11 +489,14 @@ class VecIPPEnv:
                 # (50x50 / 100x100: no [n, N] noise array written and read back), else fill + generate
                 epi = self.episode[self._reset_ids_host[p]]
                 if self._grf_rows is not False and len(epi) and np.all(epi == epi[0]):
-                    self._grf_rows = self.engine.generate_grf_rows(n, self.seed, self.GT_STREAM + int(epi[0]), self._staged_field(buf)[:n],
-                                                                   row_ids=self._reset_ids_by_phase[p], row_offset=self.env_id_offset,
-                                                                   stream=self._side)
+                    self._grf_rows = self.engine.generate_fields_rows(self.field_kind, n, self.seed, self.GT_STREAM + int(epi[0]),
+                                                                      self._staged_field(buf)[:n], row_ids=self._reset_ids_by_phase[p],
+                                                                      row_offset=self.env_id_offset, stream=self._side)
                     if self._grf_rows:
                         continue
+                if self.field_kind != _ffi.IPP_FIELD_GRF:
+                    self._fields_for(self._reset_ids_by_phase[p], self._reset_ids_host[p], self._staged_field(buf)[:n])
+                    continue
                 white = self._white_for(self._reset_ids_by_phase[p], self._reset_ids_host[p], self._staged_white_field(buf)[:n])
                 self.engine.generate_grf(white, out=self._staged_field(buf)[:n], stream=self._side)
             if upto == K:
@@ -516,8 +535,8 @@ class VecIPPEnv:
         # (2 K > episode_steps: a block is staged when its first step arrives, behind the `free` event of block b - 2 only -- while
         # block b - 1, whose resets flip the very planes this launch would write, may still be running: staged buffers + copies then)
         alt = bool(self._fused_reset) and self._gt_flip_ok and 2 * K <= self.episode_steps
-        ok = self.engine.generate_grf_rows(K * nm, self.seed, self.GT_STREAM, None if alt else self._staged_buffers()[set_], row_ids=ids,
-                                           row_offset=self.env_id_offset, stream=self._side, group_rows=nm, group_subsequence=epi)
+        ok = self.engine.generate_fields_rows(self.field_kind, K * nm, self.seed, self.GT_STREAM, None if alt else self._staged_buffers()[set_],
+                                              row_ids=ids, row_offset=self.env_id_offset, stream=self._side, group_rows=nm, group_subsequence=epi)
         if not ok:
             self._grf_rows = False
             return False
@@ -574,6 +593,23 @@ class VecIPPEnv:
             tmp = self.torch.empty((len(sel), self.cfg.n_cells), dtype=self.torch.float32, device=self.device)
             self.engine.normal_rows(tmp, self.cfg.n_cells, self.seed, self.GT_STREAM + int(e),
                                     row_ids=np.asarray(ids_host)[sel].astype(np.int32), row_offset=self.env_id_offset)
+            out[self.torch.as_tensor(sel, device=self.device)] = tmp
+        return out
+
+    def _fields_for(self, ids_dev, ids_host, out):
+        """Hotspot / split ground truths of the NEXT episode of the given envs into `out` [n, N] on the current stream: keyed like
+        _white_for (row = global env id, subsequence = GT_STREAM + that env's episode index; one launch per episode index present)."""
+        epi = self.episode[np.asarray(ids_host, dtype=np.int64)]
+        uniq = np.unique(epi)
+        if len(uniq) == 1:
+            self.engine.generate_fields_rows(self.field_kind, len(epi), self.seed, self.GT_STREAM + int(uniq[0]), out, row_ids=ids_dev,
+                                             row_offset=self.env_id_offset)
+            return out
+        for e in uniq:  # (hand-made reset sets only)
+            sel = np.nonzero(epi == e)[0]
+            tmp = self.torch.empty((len(sel), self.cfg.n_cells), dtype=self.torch.float32, device=self.device)
+            self.engine.generate_fields_rows(self.field_kind, len(sel), self.seed, self.GT_STREAM + int(e), tmp,
+                                             row_ids=np.asarray(ids_host)[sel].astype(np.int32), row_offset=self.env_id_offset)
             out[self.torch.as_tensor(sel, device=self.device)] = tmp
         return out
 
@@ -854,8 +890,8 @@ class VecIPPEnv:
                                self.status, self._part_begin, streams, init_action=INIT_ACTION)
         for p, st in enumerate(streams):
             b, e = self._part_begin[p], self._part_begin[p + 1]
-            self.engine.generate_grf_refill(e - b, self.refill[b:e], self.episode, self.seed, self.GT_STREAM, row_offset=self.env_id_offset,
-                                            stream=st)
+            self.engine.generate_fields_refill(self.field_kind, e - b, self.refill[b:e], self.episode, self.seed, self.GT_STREAM,
+                                               row_offset=self.env_id_offset, stream=st)
         self._noise_done_parts(streams)
         self.t += 1
         self._async_pending = True

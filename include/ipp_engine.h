@@ -447,6 +447,65 @@ int ipp_mcts_policy(const ipp_mcts_tables* t, const double* tie_uniform, double 
 int ipp_state_plane(void* engine, int32_t env_id, const float* mean_for_mask, uint32_t flags, float* out, void* stream);
 
 /*
+ * NN input feature planes of a batch of histories: generate_input_feature_planes (planning/common/features.py:83-151) of
+ * n requests in one launch, fp32 [n][C][N][N].  Request i has spec->history = H entries, newest first.  Entry h is a state:
+ * env slot root_env with its prior_scale, minus its first `rank` factor columns (-1 = all of them: the slot's current state;
+ * within an episode columns are only appended, so a smaller rank is an EARLIER state of the slot), minus the columns of the
+ * tree nodes on `path` (the ChainCols path of ipp_tree_step, -1 padded; only below the current rank).  Dense slots are read in
+ * place (rank ignored, no path).
+ * Channels per entry: [state, x, y, z, budget] (position mode) or [state, fov, budget] (use_fov); the cost plane follows the
+ * last entry in position mode with use_costs.  C = 5H + 1, 5H or 3H.
+ *   state   rows / columns with mean + interval_factor * diag < value_threshold zeroed (adaptive; mean = mask_mean row i, else the
+ *           CURRENT mean of slot mask_env[i]; diag = the entry's own: the slot's stored diag for its current state, the deepest
+ *           path node's node_diag, or the densified diagonal of a prefix), then min-max normalised over all N x N values
+ *           (min == max: x / max, so an all-zero plane is NaN like NumPy's)
+ *   x, y    position[0] / (x_dim * resolution), position[1] / (x_dim * resolution) (features.py:50-51)
+ *   z       (position[2] - min_altitude) / (max_altitude - min_altitude)
+ *   fov     outer(sel, sel), sel = get_field_of_view_indices: cells x_dim * x + y, x in [xl, xr), y in [yu, yd) of the footprint
+ *   budget  the entry's budget as given (remaining / initial)
+ *   cost    row c = action cost from (position[0] of entry 0, min_altitude) to cell c = x_dim * x + y at its centre, distance or
+ *           flight time (use_flight_time, ipp_set_uav), fp64 min-max normalised over the N costs
+ * Entries with valid = 0 are zero padding (entry 0 padding: zero cost plane).  An entry that names a slot, node or rank outside
+ * the engine's, a path on a dense engine or a path below a prefix gets NaN planes.  FoV and cost planes need a square grid.
+ * mask_env may be NULL when mask_mean is given or adaptive = 0.  Returns -1 on a bad spec, n outside [0, 2^20] or a grid over
+ * 65536 cells; a path on an engine without a node pool is an entry the engine cannot evaluate (NaN planes).
+ */
+typedef struct ipp_plane_entry {        /* one history entry of one request; valid = 0: zero padding */
+    int32_t root_env;                   /* env slot whose columns / prior the state starts from */
+    int32_t rank;                       /* first `rank` columns of the slot (-1 = its current rank) */
+    int32_t path[IPP_TREE_DEPTH];       /* tree nodes below the slot, -1 padded (the ChainCols path) */
+    int32_t valid, reserved;
+    double  position[3];                /* waypoint pushed with this state */
+    double  budget;                     /* already normalised (remaining / initial) */
+} ipp_plane_entry;
+
+typedef struct ipp_plane_spec {
+    int32_t history;                    /* H = input_history_length, >= 1 */
+    int32_t use_fov;                    /* 1: [state, fov, budget] per entry (min / max altitude None) */
+    int32_t use_costs;                  /* cost plane appended (position mode only, like the reference) */
+    int32_t adaptive;                   /* mask rows / columns by mean + k diag(P) >= thr */
+    int32_t use_flight_time;            /* cost plane: flight time (1) or distance (0) */
+    int32_t reserved;
+    double  min_altitude, max_altitude;
+} ipp_plane_spec;
+
+int ipp_feature_planes(void* engine, const ipp_plane_spec* spec /*[host]*/, const ipp_plane_entry* entries /*[dev] n*H*/, int32_t n,
+                       const int32_t* mask_env /*[dev] n*/, const float* mask_mean /*[dev] n*N or NULL*/, float* out /*[dev] n*C*N*N*/,
+                       void* stream);
+/*
+ * History entries of the pending leaves of a wave of ipp_mcts_select (the planes of a search's inference batch): out [dev]
+ * roots * wave * history records, slot g = root j * wave + s.  For each pending leaf: the leaf, then the nodes of the descent that
+ * reached it, deepest first (p_node / p_k / p_cost of descent pend_sim - sim0; the root node last), then root_history[j][1 ..]
+ * ([dev] roots * history records, e.g. the env's ring entries, or NULL), then zero padding.  A node's state is the root env slot
+ * plus its device path n_devpath; its position the action of the edge into it (prev0 at the root); its budget budget0 minus the
+ * descent's costs above it, over initial_budget.  mask_env [dev] roots * wave or NULL: = root_env[j] (the root env's current
+ * mean masks every entry).  Slots without a pending leaf are padding.  Call after ipp_mcts_steps, before ipp_mcts_backup.
+ */
+int ipp_mcts_plane_entries(const ipp_mcts_tables* t, const int32_t* root_env /*[dev]*/, const double* prev0 /*[dev]*/, const double* budget0 /*[dev]*/,
+                           const ipp_plane_entry* root_history /*[dev] or NULL*/, int32_t history, double initial_budget, int32_t sim0,
+                           ipp_plane_entry* out /*[dev]*/, int32_t* mask_env /*[dev] or NULL*/, void* stream);
+
+/*
  * Ground-truth generation only: white noise [n][H][W] -> min-max normalised Gaussian random field into the
  * caller buffer gt_out [n][H][W] (no env slot is touched).  Lets the host prepare the next episodes' ground
  * truths on a side stream while ipp_step runs, then install them with ipp_reset(gt = ...).

@@ -19,7 +19,7 @@ IPP_FIELD_GRF, IPP_FIELD_HOTSPOT, IPP_FIELD_SPLIT = 0, 1, 2
 STATUS_OK, STATUS_CHOL_FALLBACK, STATUS_NOT_PD, STATUS_RANK_FULL, STATUS_BAD_FOOTPRINT = 0, 1, 2, 3, 4
 IPP_MAX_MEAS = 25
 ABI_VERSION = 17
-AB_MIN_ABI = 13  # oldest library tools/ab_kernels.py may load under IPP_AB_OLD_LIB (v14 added the ipp_arena_* calls, v15 the budget ledger calls, v16 the *_prior calls, v17 the field calls; nothing else)
+AB_MIN_ABI = 13  # oldest library tools/ab_kernels.py may load under IPP_AB_OLD_LIB (v14 added the ipp_arena_* calls, v15 the budget ledger calls, v16 the *_prior calls, v17 the field calls; ipp_feature_planes and ipp_mcts_plane_entries were added later WITHOUT a bump -- tests pin 17 -- so an older v17 library lacks them and the A/B loader leaves them unbound; nothing else)
 IPP_ARENA_HIPMALLOC, IPP_ARENA_VMM = 0, 1
 
 
@@ -52,6 +52,13 @@ class IppInfo(C.Structure):
 class IppFieldRecord(C.Structure):
     """ipp_field_record: cell (y, x) = inside if it lies in rect[0] or rect[1] ({y0, y1, x0, x1}, half-open), else outside."""
     _fields_ = [("inside", C.c_double), ("outside", C.c_double), ("rect", (C.c_int32 * 4) * 2)]
+
+
+class IppPlaneSpec(C.Structure):
+    _fields_ = [
+        ("history", C.c_int32), ("use_fov", C.c_int32), ("use_costs", C.c_int32), ("adaptive", C.c_int32),
+        ("use_flight_time", C.c_int32), ("reserved", C.c_int32), ("min_altitude", C.c_double), ("max_altitude", C.c_double),
+    ]
 
 
 class IppStepItem(C.Structure):
@@ -111,6 +118,8 @@ PROTOTYPES = {
     "ipp_reset_episode": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "ipp_score_actions": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_uint32, _P, _P, _P]),
     "ipp_state_plane": (C.c_int, [_P, C.c_int32, _P, C.c_uint32, _P, _P]),
+    "ipp_feature_planes": (C.c_int, [_P, C.POINTER(IppPlaneSpec), _P, C.c_int32, _P, _P, _P, _P]),
+    "ipp_mcts_plane_entries": (C.c_int, [C.POINTER(IppMctsTables), _P, _P, _P, _P, C.c_int32, C.c_double, C.c_int32, _P, _P, _P]),
     "ipp_tree_step": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P, C.c_uint32, _P, _P, _P]),
     "ipp_tree_read_diag": (C.c_int, [_P, C.c_int32, _P, _P]),
     "ipp_mcts_select": (C.c_int, [C.POINTER(IppMctsTables), _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, _P]),

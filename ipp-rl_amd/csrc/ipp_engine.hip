@@ -27,6 +27,7 @@
 #include "k_fields.h"
 #include "k_score.h"
 #include "k_plane.h"
+#include "k_feature_planes.h"
 #include "k_tree.h"
 #include "k_tree_patch.h"
 #include "k_mcts.h"
@@ -1777,6 +1778,54 @@ int ipp_state_plane(void* engine, int32_t env_id, const float* mean_for_mask, ui
     const int blocks = std::min(v.N, 1024);
     hipLaunchKernelGGL(k_plane_minmax, dim3(blocks), dim3(256), 0, s, v, sv.P, sv.mask, sv.extent);
     hipLaunchKernelGGL(k_plane_write, dim3(blocks), dim3(256), 0, s, v, sv.P, sv.mask, sv.extent, out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ipp_feature_planes(void* engine, const ipp_plane_spec* spec, const ipp_plane_entry* entries, int32_t n, const int32_t* mask_env,
+                       const float* mask_mean, float* out, void* stream) {
+    Engine* e = as_engine(engine);
+    if (!e || !spec) return fail(-1, "null argument");
+    if (n < 0 || n > (1 << 20)) return fail(-1, "n = %d outside [0, 2^20]", n);
+    if (spec->history < 1 || spec->history > 64) return fail(-1, "history = %d outside [1, 64]", spec->history);
+    if ((spec->use_fov | spec->use_costs | spec->adaptive | spec->use_flight_time) & ~1) return fail(-1, "spec flags must be 0 or 1");
+    if (!spec->use_fov && !(std::isfinite(spec->min_altitude) && std::isfinite(spec->max_altitude) && spec->max_altitude != spec->min_altitude))
+        return fail(-1, "position mode needs finite min_altitude != max_altitude");
+    const View& v = e->v;
+    const bool costs = spec->use_costs && !spec->use_fov;
+    if ((spec->use_fov || costs) && v.W != v.H) return fail(-1, "FoV and cost planes need a square grid (cell x_dim * x + y), got %d x %d", v.W, v.H);
+    if (costs && spec->use_flight_time && !(v.vmax > 0 && v.amax > 0)) return fail(-1, "flight-time costs need max_v, max_a > 0");
+    if (spec->adaptive && !mask_env && !mask_mean) return fail(-1, "adaptive planes need mask_env or mask_mean");
+    if (n == 0) return 0;
+    if (!entries || !out) return fail(-1, "null argument");
+    const size_t mask_bytes = ((size_t)v.N + 15) & ~(size_t)15;
+    if (mask_bytes > 64 * 1024) return fail(-1, "grids over 65536 cells are not supported");
+    PlaneArgs a{};
+    a.entries = entries; a.mask_env = mask_env; a.mask_mean = mask_mean; a.out = out;
+    a.n = n; a.H = spec->history; a.cpe = spec->use_fov ? 3 : 5; a.C = a.cpe * a.H + (costs ? 1 : 0);
+    a.fov = spec->use_fov; a.costs = costs ? 1 : 0; a.adaptive = spec->adaptive; a.flight = spec->use_flight_time;
+    a.dense = v.mode == IPP_DENSE ? 1 : 0;
+    a.cache = (size_t)v.N * v.N * 4 + mask_bytes + kPlaneStaticLds <= (size_t)kPlaneLdsBytes ? 1 : 0;  // (no opt-in above 64 KB)
+    a.min_alt = spec->min_altitude; a.max_alt = spec->max_altitude;
+    const size_t lds = mask_bytes + (a.cache ? (size_t)v.N * v.N * 4 : 0);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(e->device));
+    hipLaunchKernelGGL(k_feature_planes, dim3((unsigned)n * (a.H + a.costs)), dim3(256), lds, s, v, e->tv, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ipp_mcts_plane_entries(const ipp_mcts_tables* t, const int32_t* root_env, const double* prev0, const double* budget0,
+                           const ipp_plane_entry* root_history, int32_t history, double initial_budget, int32_t sim0, ipp_plane_entry* out,
+                           int32_t* mask_env, void* stream) {
+    if (int rc = mcts_check(t)) return rc;
+    if (!root_env || !prev0 || !budget0 || !out) return fail(-1, "null argument");
+    if (history < 1 || history > 64) return fail(-1, "history = %d outside [1, 64]", history);
+    if (!(initial_budget > 0.0)) return fail(-1, "initial_budget must be > 0");
+    HIP_TRY(hipSetDevice(t->device));
+    const int n = t->roots * t->wave;
+    hipLaunchKernelGGL(k_mcts_plane_entries, dim3((n + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *t, root_env, prev0,
+                       budget0, root_history, (int)history, initial_budget, (int)sim0, out, mask_env);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -460,6 +460,37 @@ class IPPEngine:
         self._keep_plane = mu
         return out
 
+    def feature_planes(self, entries, spec, mask_env=None, mask_mean=None, out=None, stream=None):
+        """NN input planes of n histories (generate_input_feature_planes, planning/common/features.py:83-151), device fp32
+        [n, C, N, N].  entries: device int32 [n, H, 18] (feature_planes.entry_tensor / the env's and search's own builders)
+        or ENTRY_DTYPE records [n, H]; spec: feature_planes.PlaneSpec; mask_env: [n] slots whose CURRENT mean masks each
+        request, or mask_mean [n, N]."""
+        from . import feature_planes as fp
+
+        torch = _torch()
+        if not isinstance(entries, torch.Tensor):
+            entries = fp.entry_tensor(entries, self.device)
+        fp.check_entries(entries, spec.history)
+        n = int(entries.shape[0])
+        entries = entries.contiguous()
+        me = None if mask_env is None else self._dev(mask_env, torch.int32).reshape(-1)
+        mm = None if mask_mean is None else self._dev(mask_mean, torch.float32).reshape(-1)
+        if me is not None and me.numel() != n:
+            raise ValueError(f"mask_env has {me.numel()} slots for {n} requests")
+        if mm is not None and mm.numel() != n * self.n_cells:
+            raise ValueError(f"mask_mean has {mm.numel()} values for {n} x {self.n_cells}")
+        shape = (n, spec.channels, self.n_cells, self.n_cells)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError(f"out must be contiguous float32 {shape}")
+        cs = spec.to_c()
+        st = self.stream if stream is None else C.c_void_p(stream.cuda_stream)
+        _ffi.check(self._lib.ipp_feature_planes(self._h, C.byref(cs), self._ptr(entries), n, self._ptr(me), self._ptr(mm),
+                                                self._ptr(out), st))
+        self._keep_planes = (entries, me, mm)
+        return out
+
     def generate_grf(self, white_noise, out=None, stream=None):
         """white noise [n, N] -> normalised GRF [n, N] in a caller tensor (no env slot touched)."""
         torch = _torch()

@@ -22,6 +22,10 @@ streams on the device (statistically equivalent, not NumPy's streams), and the n
         prior: [n, kmax] float64 probabilities on the valid sets (need not be normalised) or None = uniform
         value: [n] float64 tensor or a float
     infer=None: uniform priors, value `leaf_value` (the stub of the benchmarks).
+    feature_planes=True adds "planes" [n, C, N, N] float32: generate_input_feature_planes of each leaf (mcts.py:178-204) with the
+    spec of hyper_params / meta_data, from the history leaf -> its ancestors on the descent -> the root's own earlier states
+    (get_policy(root_history=env.history_entries(roots))), masked with the root env's current mean; plus "entries" (the
+    ipp_plane_entry records), "search" (the DeviceMCTS whose tables "node" indexes: a group's own with groups > 1) and "root_base".
 """
 from __future__ import annotations
 
@@ -38,7 +42,7 @@ from .vector_mcts import VectorMCTS
 class DeviceMCTS(VectorMCTS):
     def __init__(self, engine, hyper_params: Dict, meta_data: Dict, infer: Optional[Callable] = None, sims_in_flight: int = 4,
                  tie_break: str = "first", seed: int = 0, leaf_value: float = 0.0, nodes_per_root: Optional[int] = None,
-                 dev_per_root: Optional[int] = None, queue_ahead: bool = True, groups: int = 2):
+                 dev_per_root: Optional[int] = None, queue_ahead: bool = True, groups: int = 2, feature_planes: bool = False):
         """groups > 1: the roots of a search are split into that many contiguous groups, each with its own node tables, whose waves of
         simulations alternate on their own streams -- one group's selection (one wavefront per SIMD: latency-bound) runs beside the
         other's tree steps, and the host's one read-back per wave of simulations waits for one group while the other's launches are
@@ -48,7 +52,21 @@ class DeviceMCTS(VectorMCTS):
         super().__init__(engine, hyper_params, meta_data, infer, None, sims_in_flight, tie_break, seed)
         self.groups = max(1, int(groups))
         self._ctor = dict(hyper_params=hyper_params, meta_data=meta_data, infer=infer, sims_in_flight=sims_in_flight, tie_break=tie_break,
-                          seed=seed, leaf_value=leaf_value, nodes_per_root=nodes_per_root, dev_per_root=dev_per_root, queue_ahead=queue_ahead)
+                          seed=seed, leaf_value=leaf_value, nodes_per_root=nodes_per_root, dev_per_root=dev_per_root, queue_ahead=queue_ahead,
+                          feature_planes=feature_planes)
+        self.plane_spec = None
+        if feature_planes:
+            from ...feature_planes import PlaneSpec
+
+            if infer is None:
+                raise ValueError("feature_planes=True needs an infer callback (the planes are its input)")
+            try:
+                self.plane_spec = PlaneSpec.from_params(hyper_params, meta_data, adaptive=self.adaptive, use_flight_time=self.uav is not None)
+                self._plane_b0 = float(meta_data.get("initial_budget", meta_data.get("budget")))
+            except (KeyError, TypeError) as exc:
+                raise ValueError(f"feature_planes=True needs input_history_length / use_fov_input in hyper_params and min_altitude, "
+                                 f"max_altitude, initial_budget (or budget) in meta_data: {exc!r}") from None
+        self._root_history = None
         self._root_base = self._dev_base = self._scratch_base = 0  # (a group's offsets in the whole search: ipp_mcts_tables)
         self._total_roots = None
         self._subs = None
@@ -154,14 +172,17 @@ class DeviceMCTS(VectorMCTS):
 
     # ------------------------------------------------------------------ search
     def get_policy(self, roots: Sequence[int], previous_actions, budgets, depth: int = 0, temperature: float = 1.0,
-                   deploy_time: bool = False, rngs=None, as_arrays: bool = False):
+                   deploy_time: bool = False, rngs=None, as_arrays: bool = False, root_history=None):
         """Like VectorMCTS.get_policy: one search of num_mcts_simulations per root, policies from the roots' visit counts.
 
         The read-out (mcts.py:83-143) runs on the device too (ipp_mcts_policy) when temperature > 0, the action set is a large one and
         the roots share one generator (rngs=None); the reference's per-root (dict, valid indices) pairs are then built from two
         arrays.  as_arrays=True skips that: returns {"policy": [R, kmax] float64, "valid_idx": [R, kmax] int32 (-1 padded),
-        "K": [R], "ok": [R] (0 where the reference returns None)} as DEVICE tensors (valid until the next search)."""
+        "K": [R], "ok": [R] (0 where the reference returns None)} as DEVICE tensors (valid until the next search).
+        root_history (feature_planes=True): device ipp_plane_entry records [R, H, 18] of the roots' histories, entry 0 = the root state
+        (VecIPPEnv.history_entries(roots)); entries 1 .. follow a leaf's ancestry in its planes.  None: the ancestry only."""
         R = len(roots)
+        self._root_history = self._check_root_history(root_history, R)
         on_device = (rngs is None and temperature > 0 and self.num_actions > self.DENSE_ACTIONS
                      and os.environ.get("IPP_MCTS_HOST_READOUT", "0") != "1")
         G = min(self.groups, R // 2)
@@ -235,7 +256,7 @@ class DeviceMCTS(VectorMCTS):
             self.stats["device_steps"] += n
             self.stats["launches"] += 1 if ahead else 0
             if n_pending:
-                self._expand(lib, tp, b, R, W, root_env, stream)
+                self._expand(lib, tp, b, R, W, root_env, stream, sim, prev0, budget0)
                 self.stats["inferences"] += n_pending
             _ffi.check(lib.ipp_mcts_backup(tp, int(w), stream))
             sim += w
@@ -299,6 +320,7 @@ class DeviceMCTS(VectorMCTS):
         for sub, n, st in zip(self._subs, sizes, self._group_streams):
             st.wait_stream(main)  # (the roots' states were written on the caller's stream)
             state = {}
+            sub._root_history = None if self._root_history is None else self._root_history[lo:lo + n].contiguous()
             gens.append(sub._search(list(roots[lo:lo + n]), prev[lo:lo + n], bud[lo:lo + n], depth, state))
             states.append(state)
             lo += n
@@ -324,7 +346,34 @@ class DeviceMCTS(VectorMCTS):
             return {k: torch.cat([o[k] for o in outs]) for k in outs[0]}
         return [p for o in outs for p in o]
 
-    def _expand(self, lib, tp, b, R, W, root_env, stream):
+    def _check_root_history(self, root_history, R):
+        if root_history is None:
+            return None
+        if self.plane_spec is None:
+            raise ValueError("root_history needs DeviceMCTS(feature_planes=True)")
+        from ...feature_planes import check_entries
+
+        check_entries(root_history, self.plane_spec.history)
+        if root_history.shape[0] != R:
+            raise ValueError(f"root_history has {root_history.shape[0]} rows for {R} roots")
+        return root_history.to(self.engine.device).contiguous()
+
+    def _leaf_planes(self, lib, tp, R, W, root_env, stream, sim, prev0, budget0, g):
+        """Entries of the wave's pending leaves (ipp_mcts_plane_entries, on the device) and their planes, rows g of the [R W] slots."""
+        import torch
+
+        from ...feature_planes import ENTRY_WORDS
+
+        spec, dev = self.plane_spec, root_env.device
+        ent_all = torch.empty((R * W, spec.history, ENTRY_WORDS), dtype=torch.int32, device=dev)
+        mask_all = torch.empty((R * W,), dtype=torch.int32, device=dev)
+        rh = self._root_history
+        _ffi.check(lib.ipp_mcts_plane_entries(tp, root_env.data_ptr(), prev0.data_ptr(), budget0.data_ptr(), rh.data_ptr() if rh is not None else None,
+                                              int(spec.history), self._plane_b0, int(sim), ent_all.data_ptr(), mask_all.data_ptr(), stream))
+        ent = ent_all[g].contiguous()
+        return ent, self.engine.feature_planes(ent, spec, mask_env=mask_all[g])
+
+    def _expand(self, lib, tp, b, R, W, root_env, stream, sim=0, prev0=None, budget0=None):
         import torch
 
         seed = C.c_uint64((self.seed * 0x9E3779B97F4A7C15 + 12345) & (2 ** 64 - 1))
@@ -340,6 +389,9 @@ class DeviceMCTS(VectorMCTS):
         batch = dict(root=root_env[(g // W)], node=nodes, depth=b["pend_depth"].reshape(-1)[g],
                      previous_action=b["pend_prev"].reshape(-1, 3)[g], budget=b["pend_budget"].reshape(-1)[g],
                      valid_idx=b["t_idx"][nodes], K=b["n_k"][nodes])
+        if self.plane_spec is not None:
+            batch["entries"], batch["planes"] = self._leaf_planes(lib, tp, R, W, root_env, stream, sim, prev0, budget0, g)
+            batch["search"], batch["root_base"], batch["sim"] = self, self._root_base, int(sim)
         prior, value = self.infer(batch)
         K = b["t_idx"].shape[1]
         pr_all = None

@@ -21,6 +21,7 @@ from __future__ import annotations
 from typing import Optional, Sequence
 
 import os
+from contextlib import nullcontext as _nullcontext
 
 import numpy as np
 
@@ -92,7 +93,7 @@ class VecIPPEnv:
                  device: str = "cuda:0", seed: int = 1234, env_id_offset: int = 0, shuffle_prior_cov: bool = False,
                  rank_cap: Optional[int] = None, stagger: bool = False, tile_threads: int = 0,
                  adaptive: bool = True, use_flight_time: bool = True, window_rows: int = 0, fused_reset: bool = True,
-                 parts: int = 1, arena=None, budget: Optional[float] = None, shuffle_budget: bool = False):
+                 parts: int = 1, arena=None, budget: Optional[float] = None, shuffle_budget: bool = False, feature_history: int = 0):
         """budget=None: episodes of exactly `episode_steps` steps on a schedule known to the host.  budget=B0: the reference's
         budget-driven episodes (planning/mcts_zero/episode_generators.py:109-150) -- `episode_steps` is max_episode_steps, every env
         carries a device-side ledger (self.budget, self.depth, self.episode, self.done) that the step kernel charges with the action
@@ -110,6 +111,8 @@ class VecIPPEnv:
         self.shuffle_prior_cov = shuffle_prior_cov
         self.adaptive, self.use_flight_time = adaptive, use_flight_time
         self.budget_mode = budget is not None
+        self.check_feature_history(feature_history, budget)
+        self.feature_history = int(feature_history)
         self.initial_budget, self.shuffle_budget = (float(budget) if budget is not None else None), bool(shuffle_budget)
         # ground-truth kind (sensor.simulation.type): hotspot / split fields are drawn on the device on every grid (fields.py)
         self.field_kind = field_kind(cfg.simulation)
@@ -268,6 +271,16 @@ class VecIPPEnv:
             self._started = False
             self.engine.set_budget(self.budget, self.depth, self.episode, self.done, self.refill, self.initial_budget,
                                    self.episode_steps, self.shuffle_budget, self.seed, self.env_id_offset)
+            if self.feature_history:
+                # NN input history (feature_history = input_history_length): per env a ring of the last H pre-step states, each as
+                # (rank, waypoint, budget / initial budget, episode) -- within an episode the factor columns are only appended, so
+                # the state of an earlier step is the column prefix of that rank (feature_planes.py)
+                Hh = self.feature_history
+                self.hist_rank = torch.zeros((B, Hh), dtype=torch.int32, device=dev)
+                self.hist_prev = torch.zeros((B, Hh, 3), dtype=torch.float64, device=dev)
+                self.hist_budget = torch.zeros((B, Hh), dtype=torch.float64, device=dev)
+                self.hist_episode = torch.full((B, Hh), -1, dtype=torch.int64, device=dev)
+                self._hist_pos = 0
 
     def _init_budget_parts(self, parts: int):
         """Budget mode, parts > 1: the fixed env groups of the scheduled mode (env e in group ((e + env_id_offset) // episode_steps) % parts),
@@ -323,12 +336,86 @@ class VecIPPEnv:
         self.refill.fill_(-1)
         self._started = True
 
+    @staticmethod
+    def check_feature_history(feature_history: int, budget) -> None:
+        """feature_history is opt-in and follows the reference's episode loop: budget mode only."""
+        if feature_history is None or int(feature_history) < 0 or int(feature_history) > 64:
+            raise ValueError(f"feature_history = {feature_history} outside [0, 64]")
+        if int(feature_history) and budget is None:
+            raise ValueError("feature_history needs budget mode (VecIPPEnv(budget=...))")
+
+    def _push_history(self, streams=None):
+        """Ring slot (pushes % H) of every env = its pre-step state, queued on the stream(s) that launch the step (parts > 1: each
+        part's envs on that part's stream, behind its previous step)."""
+        if not self.feature_history:
+            return
+        torch = self.torch
+        slot = self._hist_pos % self.feature_history
+        parts = [(None, None)] if streams is None else list(zip(streams, self._part_envs))
+        for st, idx in parts:
+            ctx = torch.cuda.stream(st) if st is not None else _nullcontext()
+            with ctx:
+                r = self.engine.ranks()
+                if idx is None:
+                    self.hist_rank[:, slot] = r[:self.num_envs]
+                    self.hist_prev[:, slot] = self.prev
+                    self.hist_budget[:, slot] = self.budget / self.initial_budget
+                    self.hist_episode[:, slot] = self.episode
+                else:
+                    self.hist_rank[idx, slot] = r[idx]
+                    self.hist_prev[idx, slot] = self.prev[idx]
+                    self.hist_budget[idx, slot] = self.budget[idx] / self.initial_budget
+                    self.hist_episode[idx, slot] = self.episode[idx]
+        self._hist_pos += 1
+
+    def history_entries(self, env_ids=None):
+        """Device ipp_plane_entry records [n, H, 18] of the envs' current histories, newest first: the current state (rank -1, the
+        current waypoint and budget), then the ring's pre-step states of the SAME episode (older ones, and every entry of an
+        earlier episode, are padding: a reset starts an empty history like a fresh EpisodeHistory)."""
+        from . import feature_planes as fp
+
+        if not self.feature_history:
+            raise ValueError("history_entries needs VecIPPEnv(feature_history=H)")
+        torch = self.torch
+        if self.parts > 1:
+            self.wait()
+        ids = torch.arange(self.num_envs, device=self.device) if env_ids is None else self.engine._dev(env_ids, torch.int64).reshape(-1)
+        Hh, n = self.feature_history, int(ids.numel())
+        ent = fp.empty_entries(n, Hh, self.device)
+        f64 = ent.view(torch.float64)
+        epi = self.episode[ids]
+        ent[:, 0, 0] = ids.to(torch.int32)
+        ent[:, 0, 1] = -1
+        ent[:, 0, fp.VALID_W] = 1
+        f64[:, 0, fp.POS_F64:fp.POS_F64 + 3] = self.prev[ids]
+        f64[:, 0, fp.BUDGET_F64] = self.budget[ids] / self.initial_budget
+        for k in range(1, Hh):
+            if self._hist_pos - k < 0:
+                break
+            slot = (self._hist_pos - k) % Hh
+            ok = self.hist_episode[ids, slot] == epi
+            ent[:, k, 0] = torch.where(ok, ids.to(torch.int32), 0)
+            ent[:, k, 1] = torch.where(ok, self.hist_rank[ids, slot], 0)
+            ent[:, k, fp.VALID_W] = ok.to(torch.int32)
+            f64[:, k, fp.POS_F64:fp.POS_F64 + 3] = torch.where(ok[:, None], self.hist_prev[ids, slot], 0.0)
+            f64[:, k, fp.BUDGET_F64] = torch.where(ok, self.hist_budget[ids, slot], 0.0)
+        return ent
+
+    def feature_planes(self, spec, out=None, env_ids=None):
+        """NN input planes of the envs' current histories (history_entries), masked with each env's CURRENT mean: the training-sample
+        input of planning/mcts_zero/episode_generators.py:157-182.  Device fp32 [n, C, N, N]."""
+        if int(spec.history) != self.feature_history:
+            raise ValueError(f"spec.history = {spec.history} != feature_history = {self.feature_history}")
+        ent = self.history_entries(env_ids)
+        return self.engine.feature_planes(ent, spec, mask_env=ent[:, 0, 0], out=out)
+
     def _step_budget(self, actions, meas_noise, auto_reset: bool):
         """One budget-mode step of the whole batch (parts == 1): the ledger is charged in the step launch, the envs it ends reset there
         (auto_reset), and the generator stages their next fields behind it on the same stream."""
         torch = self.torch
         a = self.engine._dev(actions, torch.float64).reshape(-1, 3)
         nz = meas_noise if meas_noise is not None else self._noise_plane_single()
+        self._push_history()
         self.engine.step(a, self.prev, meas_noise=nz, adaptive=self.adaptive, use_flight_time=self.use_flight_time,
                          reward_out=self.reward, status_out=self.status, update_prev=True, budget=True, reset_on_done=auto_reset,
                          init_action=INIT_ACTION)
@@ -885,6 +972,7 @@ class VecIPPEnv:
             for st in streams:
                 st.wait_event(self._ev_inputs)
         nz = self._noise_plane_parts(None if self._noise_pos else torch.cuda.current_stream(self.device), streams)
+        self._push_history(streams)
         self.engine.set_item_order(self._budget_order)
         self.engine.step_parts(a, self.prev, nz, self._flags | _ffi.IPP_UPDATE_PREV | _ffi.IPP_BUDGET | _ffi.IPP_RESET_ON_DONE, self.reward,
                                self.status, self._part_begin, streams, init_action=INIT_ACTION)

@@ -735,6 +735,74 @@ int ipp_streamed_bytes_detail(void* engine, uint64_t* bytes /*[host]*/, uint64_t
  * to move, a lower bound of `bytes` (which charges a stored row on every cell of the unit that meets it).  0 for other engines. */
 int ipp_streamed_bytes_needed(void* engine, uint64_t* bytes /*[host]*/);
 
+/*
+ * Batched self-play (csrc/k_selfplay.h): the sample bookkeeping of the reference's episode loop, planning/mcts_zero/episode_generators.py:
+ * 102-184, for every env of a budget-mode batch at once, and the minibatch of its replay buffer (replay_buffers.py:58-101), with the data on
+ * the device.  The roots of the search are the env slots; the samples live in a ring of `slots` x num_envs rows: the sample env e
+ * records at self-play step t is row (t mod slots) num_envs + e.  A row is pending from its record until its episode ends; the commit
+ * of that episode writes its value target and marks it committed (sampleable); a record into the row clears the mark.
+ * Draws are Philox4x32-10 uniforms (word 0 + 0.5) / 2^32 under the key `seed`, keyed on the GLOBAL env id g = e + row_offset and the
+ * env's episode j and depth d (counter (g << 20) + d, subsequence stream + j; the first waypoint: counter g), so shards agree:
+ */
+#define IPP_SP_ACTION_STREAM (4ull << 40) /* the action: np.random.choice(len(policy), p=policy) (:135)                         */
+#define IPP_SP_INIT_STREAM   (5ull << 40) /* the episode's first waypoint: sample_init_action (:51, :60-62)                     */
+#define IPP_SP_TIE_STREAM    (6ull << 40) /* the kept action among the most visited ones of the forced-playout take-back (mcts.py:100) */
+#define IPP_SP_ARGMAX_STREAM (7ull << 40) /* the temperature-0 arg-max among equally visited actions (mcts.py:134-138)         */
+#define IPP_REPLAY_STREAM    (8ull << 40) /* minibatch draws: counter = draw index, subsequence = stream + the buffer's draw count */
+
+typedef struct ipp_selfplay {
+    int32_t num_envs;        /* B: env slots = search roots                                                          */
+    int32_t slots;           /* S: ring rows = S x B, S > max_episode_steps                                          */
+    int32_t kmax;            /* width of the valid-action rows (ipp_mcts_tables.kmax), <= 2048                       */
+    int32_t num_actions;     /* A                                                                                    */
+    int32_t horizon;         /* episode_horizon: terms of a value target (:162)                                      */
+    int32_t temp_threshold;  /* temperature_threshold: depth >= it is a temperature-0 step (:118-120)                */
+    int32_t temp_zero;       /* 1: temperature_scale == 0 (every step is a temperature-0 step)                       */
+    int32_t random_init;     /* 1: a new episode starts at a uniformly drawn waypoint, 0: at Mission.init_action     */
+    int32_t device;
+    int32_t reserved;
+    double  gamma;
+    uint64_t seed;
+    int64_t row_offset;      /* global id of env slot 0                                                              */
+    const double* actions;   /* [dev] [A][3] waypoints in the reference's enumeration                                */
+    /* the env batch's ledger (ipp_set_budget) and step outputs, [dev] per env */
+    double* budget; int32_t* depth; int64_t* episode; uint8_t* done; double* prev; const float* reward;
+    /* per env [dev]: samples of the running episode, forced end, next step's tie uniform, value of the episode that ended in the last
+     * step (NaN: none), the step's action and its index (-1: no policy) */
+    int32_t* ep_len; uint8_t* forced; double* tie_u; double* episode_value; double* action; int32_t* action_idx;
+    /* the ring [dev]: [S B][kmax] fp32 probabilities and valid indices (-1 padded), [S B] value target, reward, flags (1 pending, 2 committed) */
+    float* r_policy; int32_t* r_idx; double* r_value; double* r_reward; uint8_t* r_flags;
+} ipp_selfplay;
+
+/*
+ * Record the samples of self-play step `step` (before the env step; the planes are written into the ring by ipp_feature_planes).  Per env:
+ * ok[e] == 0 (get_policy returned None, :130-131): no sample, budget[e] <- 0 so that the following budget step ends the episode and resets the
+ * env in its own launch, action = the current waypoint.  Otherwise the policy is policy_t's row (ipp_mcts_policy at temperature_scale) or,
+ * for a temperature-0 step, the one-hot arg-max of policy_1's row (ipp_mcts_policy at temperature 1: the forced-playout-pruned visits over
+ * their sum; ties by an IPP_SP_ARGMAX_STREAM draw); the action index is the inverse CDF of that policy in ascending action order at an
+ * IPP_SP_ACTION_STREAM uniform (:135) and action[e] its waypoint (:136).  valid_idx [dev] [B][kmax] (ipp_mcts_policy's), ok [dev] [B].
+ */
+int ipp_selfplay_record(const ipp_selfplay* sp, int64_t step, const double* policy_t, const double* policy_1, const int32_t* valid_idx,
+                        const int32_t* ok, void* stream);
+/*
+ * After the budget step of self-play step `step`: reward[e] into the env's row; for every env whose episode ended (done, or no policy) the
+ * targets of all its rows, value_i = scale_value_target(sum_{j=i}^{min(i+horizon,T)-1} gamma^j r_j) with the ABSOLUTE step j as exponent
+ * (episode_generators.py:162-164), then their committed flags; episode_value[e] = sum_j gamma^j r_j (:158); with random_init the new
+ * episode's first waypoint into prev[e] (:51, :60-62); tie_u[e] for the next step.
+ */
+int ipp_selfplay_commit(const ipp_selfplay* sp, int64_t step, void* stream);
+/*
+ * A minibatch of n rows drawn uniformly with replacement from the committed rows (committed_cum [dev] int32 [S B]: inclusive prefix count
+ * of the committed flags) and `copies` - 1 augmented copies of it (replay_buffers.py:58-101), originals first.  Draw i takes counter i of
+ * subsequence `subsequence`; copy c >= 1 is shifted by one offset (i, j) in [0, 8]^2 (counters 2^32 + 2c, + 1) for the whole copy: plane
+ * = ReplicationPad2d(4) then the crop at (i, j).  Outputs [dev], row o = copy x n + draw: states [o][C][side][side] (planes [S B][C][side]
+ * [side], both NULL when channels == 0), policy [o][A] float, mask [o][A] uint8, value / reward [o] double, index [o] int64 (the ring
+ * row; -1 and NaN when nothing is committed), offsets [copies][2] int32.
+ */
+int ipp_replay_gather(const ipp_selfplay* sp, int32_t n, int32_t copies, int32_t channels, int32_t side, const float* planes,
+                      const int32_t* committed_cum, uint64_t seed, uint64_t subsequence, float* states, float* policy, uint8_t* mask,
+                      double* value, double* reward, int64_t* index, int32_t* offsets, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,9 @@ IPP_PRIOR_MATERN32, IPP_PRIOR_MATERN12, IPP_PRIOR_MATERN52, IPP_PRIOR_RBF = 0, 1
 IPP_COV_ONLY, IPP_PREDICT_ONLY, IPP_ADAPTIVE, IPP_USE_FLIGHT_TIME, IPP_GIVEN_OBSERVATION, IPP_UPDATE_PREV = 1, 2, 4, 8, 16, 32
 IPP_BUDGET, IPP_RESET_ON_DONE = 64, 128
 IPP_BUDGET_STREAM = 3 << 40
+# Philox subsequence bases of the self-play draws (ipp_selfplay_record / _commit, ipp_replay_gather)
+IPP_SP_ACTION_STREAM, IPP_SP_INIT_STREAM, IPP_SP_TIE_STREAM, IPP_SP_ARGMAX_STREAM, IPP_REPLAY_STREAM = (4 << 40, 5 << 40, 6 << 40, 7 << 40,
+                                                                                                       8 << 40)
 IPP_FIELD_GRF, IPP_FIELD_HOTSPOT, IPP_FIELD_SPLIT = 0, 1, 2
 STATUS_OK, STATUS_CHOL_FALLBACK, STATUS_NOT_PD, STATUS_RANK_FULL, STATUS_BAD_FOOTPRINT = 0, 1, 2, 3, 4
 IPP_MAX_MEAS = 25
@@ -102,6 +105,18 @@ class IppMctsTables(C.Structure):
         ("root_base", C.c_int32), ("dev_base", C.c_int32), ("scratch_base", C.c_int32), ("reserved0", C.c_int32),
     ]
 
+
+class IppSelfPlay(C.Structure):
+    """ipp_selfplay (include/ipp_engine.h): the batch's self-play state and sample ring, [dev] pointers."""
+    _fields_ = [
+        ("num_envs", C.c_int32), ("slots", C.c_int32), ("kmax", C.c_int32), ("num_actions", C.c_int32),
+        ("horizon", C.c_int32), ("temp_threshold", C.c_int32), ("temp_zero", C.c_int32), ("random_init", C.c_int32),
+        ("device", C.c_int32), ("reserved", C.c_int32), ("gamma", C.c_double), ("seed", C.c_uint64), ("row_offset", C.c_int64),
+        ("actions", _P), ("budget", _P), ("depth", _P), ("episode", _P), ("done", _P), ("prev", _P), ("reward", _P),
+        ("ep_len", _P), ("forced", _P), ("tie_u", _P), ("episode_value", _P), ("action", _P), ("action_idx", _P),
+        ("r_policy", _P), ("r_idx", _P), ("r_value", _P), ("r_reward", _P), ("r_flags", _P),
+    ]
+
 # name -> (restype, argtypes); exactly the symbols include/ipp_engine.h declares
 PROTOTYPES = {
     "ipp_abi_version": (C.c_int, []),
@@ -172,6 +187,10 @@ PROTOTYPES = {
     "ipp_profile_enable": (C.c_int, [_P, C.c_int32]),
     "ipp_profile_read": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]),
     "ipp_profile_read_busy": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]),
+    "ipp_selfplay_record": (C.c_int, [C.POINTER(IppSelfPlay), C.c_int64, _P, _P, _P, _P, _P]),
+    "ipp_selfplay_commit": (C.c_int, [C.POINTER(IppSelfPlay), C.c_int64, _P]),
+    "ipp_replay_gather": (C.c_int, [C.POINTER(IppSelfPlay), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_uint64, C.c_uint64,
+                                    _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -31,6 +31,7 @@
 #include "k_tree.h"
 #include "k_tree_patch.h"
 #include "k_mcts.h"
+#include "k_selfplay.h"
 #include "k_prepare.h"
 
 using namespace ipp;
@@ -1826,6 +1827,64 @@ int ipp_mcts_plane_entries(const ipp_mcts_tables* t, const int32_t* root_env, co
     const int n = t->roots * t->wave;
     hipLaunchKernelGGL(k_mcts_plane_entries, dim3((n + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *t, root_env, prev0,
                        budget0, root_history, (int)history, initial_budget, (int)sim0, out, mask_env);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+namespace {
+int selfplay_check(const ipp_selfplay* sp) {
+    if (!sp) return fail(-1, "null argument");
+    if (sp->num_envs <= 0 || sp->slots <= 0 || (long long)sp->num_envs * sp->slots > INT32_MAX)
+        return fail(-1, "num_envs = %d, slots = %d: need both > 0 and a ring of < 2^31 rows", sp->num_envs, sp->slots);
+    if (sp->kmax <= 0 || sp->kmax > kSpMaxK) return fail(-1, "kmax = %d outside [1, %d]", sp->kmax, kSpMaxK);
+    if (sp->num_actions <= 0 || sp->horizon < 0) return fail(-1, "num_actions = %d, horizon = %d", sp->num_actions, sp->horizon);
+    if (!sp->actions || !sp->budget || !sp->depth || !sp->episode || !sp->done || !sp->prev || !sp->reward || !sp->ep_len || !sp->forced ||
+        !sp->tie_u || !sp->episode_value || !sp->action || !sp->action_idx || !sp->r_policy || !sp->r_idx || !sp->r_value || !sp->r_reward ||
+        !sp->r_flags)
+        return fail(-1, "ipp_selfplay: null device pointer");
+    return 0;
+}
+}  // namespace
+
+int ipp_selfplay_record(const ipp_selfplay* sp, int64_t step, const double* policy_t, const double* policy_1, const int32_t* valid_idx,
+                        const int32_t* ok, void* stream) {
+    if (int rc = selfplay_check(sp)) return rc;
+    if (step < 0) return fail(-1, "step = %lld < 0", (long long)step);
+    if (!policy_t || !policy_1 || !valid_idx || !ok) return fail(-1, "null argument");
+    HIP_TRY(hipSetDevice(sp->device));
+    const size_t lds = (size_t)sp->kmax * (sizeof(double) + sizeof(int32_t));
+    hipLaunchKernelGGL(k_sp_record, dim3(sp->num_envs), dim3(kWave), lds, reinterpret_cast<hipStream_t>(stream), *sp, (long long)step, policy_t,
+                       policy_1, valid_idx, ok);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ipp_selfplay_commit(const ipp_selfplay* sp, int64_t step, void* stream) {
+    if (int rc = selfplay_check(sp)) return rc;
+    if (step < 0) return fail(-1, "step = %lld < 0", (long long)step);
+    HIP_TRY(hipSetDevice(sp->device));
+    hipLaunchKernelGGL(k_sp_commit, dim3(sp->num_envs), dim3(kWave), 0, reinterpret_cast<hipStream_t>(stream), *sp, (long long)step);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ipp_replay_gather(const ipp_selfplay* sp, int32_t n, int32_t copies, int32_t channels, int32_t side, const float* planes,
+                      const int32_t* committed_cum, uint64_t seed, uint64_t subsequence, float* states, float* policy, uint8_t* mask,
+                      double* value, double* reward, int64_t* index, int32_t* offsets, void* stream) {
+    if (int rc = selfplay_check(sp)) return rc;
+    if (n < 1 || copies < 1 || channels < 0) return fail(-1, "n = %d, copies = %d, channels = %d", n, copies, channels);
+    if (channels > 0 && (side < 1 || !planes || !states)) return fail(-1, "planes need side >= 1 and the planes / states buffers");
+    if (!committed_cum || !policy || !mask || !value || !reward || !index || !offsets) return fail(-1, "null argument");
+    const long long blocks = (long long)n * copies * (channels + 1);
+    if (blocks > INT32_MAX) return fail(-1, "%lld blocks: minibatch too large", blocks);
+    SpGather g{};
+    g.n = n; g.copies = copies; g.C = channels; g.side = side; g.A = sp->num_actions; g.kmax = sp->kmax;
+    g.cap = (long long)sp->num_envs * sp->slots;
+    g.cum = committed_cum; g.planes = planes; g.seed = seed; g.subseq = subsequence;
+    g.states = states; g.policy = policy; g.mask = mask; g.value = value; g.reward = reward; g.index = index; g.offsets = offsets;
+    HIP_TRY(hipSetDevice(sp->device));
+    const size_t lds = (size_t)sp->kmax * (sizeof(float) + sizeof(int32_t));
+    hipLaunchKernelGGL(k_sp_gather, dim3((unsigned)blocks), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), *sp, g);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -1,0 +1,1 @@
+from .selfplay import ReplayBuffer, SelfPlay  # noqa: F401

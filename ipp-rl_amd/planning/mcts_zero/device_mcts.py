@@ -68,6 +68,7 @@ class DeviceMCTS(VectorMCTS):
                                  f"max_altitude, initial_budget (or budget) in meta_data: {exc!r}") from None
         self._root_history = None
         self._root_base = self._dev_base = self._scratch_base = 0  # (a group's offsets in the whole search: ipp_mcts_tables)
+        self._key_base = 0  # (added to root_base in the tables: the number of root 0 in the draws' keys, e.g. a shard's first global env id)
         self._total_roots = None
         self._subs = None
         self._group_streams = None
@@ -146,7 +147,7 @@ class DeviceMCTS(VectorMCTS):
             num_actions=self.num_actions, use_flight_time=1 if uav is not None else 0, tie_break=0 if self.tie_break == "first" else 1,
             device=dev.index or 0, res=self._res, max_dist=self.max_dist, gamma=self.gamma, puct_init=self.puct_init,
             puct_base=self.puct_base, fpf=self.fpf, vmax=float(uav["max_v"]) if uav else 1.0, amax=float(uav["max_a"]) if uav else 1.0,
-            root_base=self._root_base, dev_base=self._dev_base, scratch_base=self._scratch_base)
+            root_base=self._root_base + self._key_base, dev_base=self._dev_base, scratch_base=self._scratch_base)
         for name in ("actions", "cell_action", "off_x", "off_y", "zkey"):
             setattr(tab, name, geo[name].data_ptr())
         tab.uniform_ps = geo["uniform"].data_ptr()
@@ -208,9 +209,16 @@ class DeviceMCTS(VectorMCTS):
         if self._tab is None or self._tab_roots != R or self._tab_depth != D:
             self._alloc(R, D)
         tab, b = self._tab, self._buf
-        prev0 = torch.as_tensor(np.asarray(previous_actions, dtype=np.float64).reshape(R, 3), device=dev)
-        budget0 = torch.as_tensor(np.asarray(budgets, dtype=np.float64).reshape(R), device=dev)
-        root_env = torch.as_tensor(np.asarray(roots, dtype=np.int32), device=dev)
+        if torch.is_tensor(previous_actions):  # (device tensors, search_device: no host copy in front of the search)
+            prev0 = previous_actions.to(dev, torch.float64).reshape(R, 3).contiguous()
+            budget0 = budgets.to(dev, torch.float64).reshape(R).contiguous()
+        else:
+            prev0 = torch.as_tensor(np.asarray(previous_actions, dtype=np.float64).reshape(R, 3), device=dev)
+            budget0 = torch.as_tensor(np.asarray(budgets, dtype=np.float64).reshape(R), device=dev)
+        if torch.is_tensor(roots):
+            root_env = roots.to(dev, torch.int32).contiguous()
+        else:
+            root_env = torch.as_tensor(np.asarray(roots, dtype=np.int32), device=dev)
         npr = self.nodes_per_root
         root_nodes = torch.arange(R, device=dev, dtype=torch.int64) * npr
         # ---- start of a search (include/ipp_engine.h: contract of ipp_mcts_tables)
@@ -282,6 +290,7 @@ class DeviceMCTS(VectorMCTS):
                 sub = DeviceMCTS(self.engine, groups=1, **self._ctor)
                 sub.nodes_per_root, sub.dev_per_root = self.nodes_per_root, self.dev_per_root
                 sub._root_base, sub._dev_base, sub._scratch_base = base, base * self.dev_per_root, base * self.sims_in_flight
+                sub._key_base = self._key_base
                 sub._total_roots, sub._group_size = R, n
                 sub.stats = self.stats  # (one set of counters for the whole search)
                 self._subs.append(sub)
@@ -308,21 +317,24 @@ class DeviceMCTS(VectorMCTS):
             self._group_streams = got
         return sizes
 
-    def _get_policy_groups(self, G, roots, previous_actions, budgets, depth, temperature, deploy_time, as_arrays):
+    def _run_groups(self, G, roots, previous_actions, budgets, depth, readout):
+        """The search in G groups of roots, each on its own stream: every group's waves of simulations are issued in turns (a turn =
+        everything a group can issue before its next wait), then readout(sub, state, lo, n) runs on the group's stream and the
+        caller's stream joins it.  previous_actions / budgets: [R, 3] / [R] arrays or device tensors.  Returns the read-outs in group
+        order."""
         import torch
 
         R = len(roots)
         sizes = self._group_setup(G, R)
-        prev = np.asarray(previous_actions, dtype=np.float64).reshape(R, 3)
-        bud = np.asarray(budgets, dtype=np.float64).reshape(R)
         main = torch.cuda.current_stream(self.engine.device)
-        gens, states, lo = [], [], 0
+        gens, parts, lo = [], [], 0
         for sub, n, st in zip(self._subs, sizes, self._group_streams):
             st.wait_stream(main)  # (the roots' states were written on the caller's stream)
             state = {}
             sub._root_history = None if self._root_history is None else self._root_history[lo:lo + n].contiguous()
-            gens.append(sub._search(list(roots[lo:lo + n]), prev[lo:lo + n], bud[lo:lo + n], depth, state))
-            states.append(state)
+            sub_roots = roots[lo:lo + n] if torch.is_tensor(roots) else list(roots[lo:lo + n])
+            gens.append(sub._search(sub_roots, previous_actions[lo:lo + n], budgets[lo:lo + n], depth, state))
+            parts.append((sub, st, lo, n, state))
             lo += n
         alive = list(range(G))
         while alive:  # a turn = everything a group can issue before its next wait: the other groups' launches are queued by then
@@ -333,18 +345,74 @@ class DeviceMCTS(VectorMCTS):
                     except StopIteration:
                         alive.remove(g)
         outs = []
-        for sub, n, st, state in zip(self._subs, sizes, self._group_streams, states):
+        for sub, st, lo, n, state in parts:
             with torch.cuda.stream(st):
-                outs.append(sub._policies(state["b"], n, self.nodes_per_root, state["prev0"], state["budget0"], temperature, deploy_time, None,
-                                          None, as_arrays))
+                outs.append(readout(sub, state, lo, n))
             main.wait_stream(st)
-        self.stats["nodes"] = sum(sub._nodes_last for sub in self._subs)
         self._subs_used = self._subs
         self._host_rows = {}
         self.root_ids = np.arange(R)
+        return outs
+
+    def _get_policy_groups(self, G, roots, previous_actions, budgets, depth, temperature, deploy_time, as_arrays):
+        import torch
+
+        R = len(roots)
+        prev = np.asarray(previous_actions, dtype=np.float64).reshape(R, 3)
+        bud = np.asarray(budgets, dtype=np.float64).reshape(R)
+        outs = self._run_groups(G, roots, prev, bud, depth, lambda sub, state, lo, n: sub._policies(
+            state["b"], n, self.nodes_per_root, state["prev0"], state["budget0"], temperature, deploy_time, None, None, as_arrays))
+        self.stats["nodes"] = sum(sub._nodes_last for sub in self._subs)
         if as_arrays:
             return {k: torch.cat([o[k] for o in outs]) for k in outs[0]}
         return [p for o in outs for p in o]
+
+    def search_device(self, roots, previous_actions, budgets, temperatures: Sequence[float], tie_uniform, depth: int = 0,
+                      root_history=None):
+        """One search per root and the read-out ON THE DEVICE (ipp_mcts_policy) at each temperature > 0 of `temperatures`, whatever the
+        number of actions: the self-play loop's search (selfplay.py).  roots: device int32 tensor of env slots; previous_actions [R, 3] and
+        budgets [R]: device tensors -- nothing is copied from the host, so the waves' count read-backs are the only synchronisations.
+        tie_uniform: device float64 [R], the uniform that keeps one of the most visited actions in the forced-playout take-back
+        (mcts.py:100).  Returns {"policy": [one [R, kmax] float64 tensor per temperature], "valid_idx": [R, kmax], "ok": [R]} (device
+        tensors, valid until the next search)."""
+        import torch
+
+        R = int(roots.numel())
+        self._root_history = self._check_root_history(root_history, R)
+        temps = [float(x) for x in temperatures]
+        if not temps or min(temps) <= 0:
+            raise ValueError(f"temperatures {temps}: the device read-out is the one for temperature > 0")
+        G = min(self.groups, R // 2)
+        if G > 1 and self.queue_ahead and bool(int(self.engine.info.patch_layout)) and self.engine.max_batch >= R * self.sims_in_flight:
+            outs = self._run_groups(G, roots, previous_actions, budgets, depth,
+                                    lambda sub, state, lo, n: sub._readout_device(state["b"], n, temps, tie_uniform[lo:lo + n]))
+            return {"policy": [torch.cat([o["policy"][i] for o in outs]) for i in range(len(temps))],
+                    "valid_idx": torch.cat([o["valid_idx"] for o in outs]), "ok": torch.cat([o["ok"] for o in outs])}
+        self._subs_used = None
+        state = {}
+        for _ in self._search(roots, previous_actions, budgets, depth, state):
+            pass
+        self._host_rows = {}
+        self._rows_src = (state["b"], R, self.nodes_per_root)
+        self.root_ids = np.arange(R)
+        return self._readout_device(state["b"], R, temps, tie_uniform)
+
+    def _readout_device(self, b, R, temps, tie_uniform):
+        """ipp_mcts_policy of this table set at each temperature (one output buffer per temperature), with the caller's tie uniforms."""
+        import torch
+
+        o = self._out
+        pols = o.setdefault("policies", [])
+        while len(pols) < len(temps):
+            pols.append(torch.empty_like(o["policy"]))
+        u = tie_uniform.to(torch.float64).contiguous()
+        self._keep_tie = u
+        for T, pol in zip(temps, pols):
+            _ffi.check(self.engine._lib.ipp_mcts_policy(C.byref(self._tab), u.data_ptr(), float(T), 0, pol.data_ptr(), o["valid_idx"].data_ptr(),
+                                                        o["ok"].data_ptr(), self.engine.stream))
+        self._rows_src = (b, R, self.nodes_per_root)
+        self._host_rows = {}
+        return {"policy": pols[:len(temps)], "valid_idx": o["valid_idx"], "ok": o["ok"]}
 
     def _check_root_history(self, root_history, R):
         if root_history is None:

@@ -1,0 +1,353 @@
+"""
+SelfPlay: the reference's self-play loop (planning/mcts_zero/episode_generators.py:102-184 -- there one EpisodeGenerator per episode and
+CPU worker, mcts_zero_mission.py:71-83) for a whole batch of budget-mode envs on one device, and ReplayBuffer: its training samples
+(input_feature_planes, policy, value, reward, valid_actions_msk) kept in device memory and served as minibatches like
+replay_buffers.py:58-101 serves the bz2 pickles.
+
+One SelfPlay.step() is one iteration of the reference's episode loop for every env:
+
+    planes    VecIPPEnv.feature_planes of each env's history (the pushed states of this episode, masked with the PRE-step mean: what
+              adaptive_info_history[i] holds, :133) straight into the env's ring row                                   (ipp_feature_planes)
+    search    DeviceMCTS on the env slots as roots, root depth 0 (:121-128); the read-out on the device (ipp_mcts_policy) for every
+              action count, at temperature_scale and, where a temperature-0 step can occur, at 1 (its arg-max)
+    record    temperature 0: one-hot arg-max (mcts.py:134-138); the action by the inverse CDF of the policy (np.random.choice, :135);
+              the sparse policy and valid set into the row; a root without a policy ends its episode (:130-131)  (ipp_selfplay_record)
+    step      VecIPPEnv.step: the fused budget step, episode ends and resets in the same launch (:137-150)
+    commit    the rewards; for every episode that ended its windowed value targets (:158-164), the rows become sampleable; the next
+              episode's first waypoint (sample_init_action, :51)                                                     (ipp_selfplay_commit)
+
+Nothing in the loop reads the device from the host beyond the search's one count read-back per wave of simulations.
+
+Draws (include/ipp_engine.h, IPP_SP_*_STREAM): the loop's own draws are Philox4x32-10 uniforms keyed on (seed, global env id, episode,
+depth); the search's draws (Dirichlet noise, random tie breaks: k_mcts.h hashes) are keyed on env_id_offset + root; so N shards with
+contiguous env_id_offset produce the samples of one process.  Minibatch draws are keyed on the buffer's draw count and the draw index.  Ring: S step slots of B rows, the sample of env e at step t in row
+(t mod S) B + e; S > max_episode_steps keeps every row of a running episode.  Replay minibatches: ReplayBuffer.sample.
+
+Divergences from the reference (INTEGRATION.md "Batched self-play"): a temperature-0 sample stores the real valid-action mask where the
+reference stores the visit counts (mcts.py:138); no prioritised replay, no tree reuse between steps, no per-episode shuffled priors; the
+draws are counter-based, not NumPy's global stream.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Callable, Dict, Optional
+
+import numpy as np
+
+from ... import _ffi
+from ...vec_env import VecIPPEnv, philox_uniform
+
+PENDING, COMMITTED = 1, 2
+ACTION_STREAM, INIT_STREAM, TIE_STREAM = _ffi.IPP_SP_ACTION_STREAM, _ffi.IPP_SP_INIT_STREAM, _ffi.IPP_SP_TIE_STREAM
+ARGMAX_STREAM, REPLAY_STREAM = _ffi.IPP_SP_ARGMAX_STREAM, _ffi.IPP_REPLAY_STREAM
+MAX_DEPTH = 1 << 20  # (the depth is the low 20 bits of a step draw's counter)
+MAX_KMAX = 2048      # widest valid set a ring row holds (csrc/k_selfplay.h kSpMaxK)
+
+
+# ---------------------------------------------------------------------------------------------------- host restatements
+def step_counter(global_env_ids, depth) -> np.ndarray:
+    """Philox counter of an env's per-step draws: (global env id << 20) + depth."""
+    return (np.asarray(global_env_ids, dtype=np.int64) << 20) + np.asarray(depth, dtype=np.int64)
+
+
+def step_uniform(stream: int, seed: int, global_env_ids, episode, depth) -> np.ndarray:
+    """The uniform an env draws at (episode, depth) from `stream` (ACTION_STREAM, TIE_STREAM, ARGMAX_STREAM)."""
+    return philox_uniform(step_counter(global_env_ids, depth), stream + np.asarray(episode, dtype=np.int64), seed)
+
+
+def init_action_index(seed: int, global_env_ids, episode, num_actions: int) -> np.ndarray:
+    """First waypoint (action index) of an episode: sample_init_action (episode_generators.py:60-62) from INIT_STREAM."""
+    u = philox_uniform(np.asarray(global_env_ids, dtype=np.int64), INIT_STREAM + np.asarray(episode, dtype=np.int64), seed)
+    return np.minimum((u * num_actions).astype(np.int64), num_actions - 1)
+
+
+def inverse_cdf(policy, u: float) -> int:
+    """np.random.choice(len(policy), p=policy) at the uniform u: the first index whose normalised cumulative sum exceeds u."""
+    cdf = np.cumsum(np.asarray(policy, dtype=np.float64))
+    cdf /= cdf[-1]
+    return int(np.searchsorted(cdf, u, side="right"))
+
+
+def value_targets(rewards, gamma: float, horizon: int):
+    """(targets, total_episode_value) of one episode: value_i = scale_value_target(sum_{j=i}^{min(i+horizon,T)-1} gamma^j r_j) with the
+    ABSOLUTE step j as exponent, the reference's own form (episode_generators.py:158-164; a discount relative to i would be gamma^(j-i))."""
+    r = [float(x) for x in rewards]
+    T = len(r)
+    out = np.empty(T)
+    for i in range(T):
+        v = 0.0
+        for j in range(i, min(i + horizon, T)):
+            v += gamma ** j * r[j]
+        out[i] = np.sqrt(1 + v) - 1
+    tot = 0.0
+    for j in range(T):
+        tot += gamma ** j * r[j]
+    return out, tot
+
+
+def replay_draws(n: int, copies: int, seed: int, draw: int, committed_rows: np.ndarray):
+    """Rows and shift offsets of minibatch number `draw` (ipp_replay_gather): draw i picks committed_rows[floor(u_i total)] (ascending
+    row order), copy c >= 1 is shifted by (i, j) in [0, 8]^2, copy 0 is (4, 4) = unshifted."""
+    sub = REPLAY_STREAM + int(draw)
+    total = len(committed_rows)
+    u = philox_uniform(np.arange(n, dtype=np.int64), sub, seed)
+    pick = np.minimum((u * total).astype(np.int64), total - 1)
+    rows = np.asarray(committed_rows, dtype=np.int64)[pick]
+    offs = np.full((copies, 2), 4, dtype=np.int64)
+    for c in range(1, copies):
+        for w in range(2):
+            uo = philox_uniform((1 << 32) + 2 * c + w, sub, seed)
+            offs[c, w] = min(int(uo * 9.0), 8)
+    return rows, offs
+
+
+def shift_planes(states: np.ndarray, offset) -> np.ndarray:
+    """ReplicationPad2d(4) followed by the crop at (i, j) of the original size (RandomCrop with one offset for the whole 4-D batch)."""
+    i, j = int(offset[0]), int(offset[1])
+    h, w = states.shape[-2:]
+    pad = np.pad(states, [(0, 0)] * (states.ndim - 2) + [(4, 4), (4, 4)], mode="edge")
+    return pad[..., i:i + h, j:j + w]
+
+
+def check_args(hyper_params: Dict, meta_data: Dict, num_envs: int, capacity: Optional[int]):
+    """What SelfPlay cannot run, refused before anything touches the device.  Returns (slots S, max_episode_steps)."""
+    if meta_data.get("initial_budget") is None:
+        raise ValueError("self-play runs budget-mode episodes: meta_data['initial_budget'] is needed")
+    if not hyper_params.get("reset_mcts_each_step", True):
+        raise ValueError("reset_mcts_each_step=False (tree reuse across steps) is not supported")
+    if hyper_params.get("use_per", False):
+        raise ValueError("use_per=True (prioritised replay) is not supported")
+    if hyper_params.get("shuffle_prior_cov", False):
+        raise ValueError("shuffle_prior_cov=True (per-episode shuffled priors) is not supported in budget mode")
+    steps = int(meta_data.get("max_episode_steps", hyper_params.get("max_episode_steps", 0)))
+    if steps < 1 or steps >= MAX_DEPTH:
+        raise ValueError(f"max_episode_steps = {steps} outside [1, 2^20)")
+    B = int(num_envs)
+    if B < 1:
+        raise ValueError("num_envs must be >= 1")
+    cap = int(capacity) if capacity is not None else B * (steps + 1)
+    if cap % B:
+        raise ValueError(f"capacity {cap} is not a multiple of num_envs {B} (the ring holds S step slots of num_envs rows)")
+    S = cap // B
+    if S < steps + 1:
+        raise ValueError(f"capacity {cap} = {S} step slots of {B} rows: at least max_episode_steps + 1 = {steps + 1} slots are needed")
+    return S, steps
+
+
+# ---------------------------------------------------------------------------------------------------- replay buffer
+class ReplayBuffer:
+    """The samples of a SelfPlay batch in device memory: S x B rows of planes [C, N, N] fp32 (channels > 0), sparse policy (fp32 on the
+    kmax slots of the root's valid set), valid set (int32, -1 padded), value target, reward (fp64) and a flag (1 pending, 2 committed).
+    sample() draws from the committed rows only."""
+
+    def __init__(self, owner: "SelfPlay", slots: int, num_envs: int, kmax: int, num_actions: int, channels: int, side: int, seed: int,
+                 device):
+        import torch
+
+        self.torch = torch
+        self.slots, self.num_envs, self.kmax, self.num_actions = int(slots), int(num_envs), int(kmax), int(num_actions)
+        self.channels, self.side, self.seed = int(channels), int(side), int(seed)
+        cap = self.capacity = self.slots * self.num_envs
+        e = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)  # noqa: E731
+        self.planes = None
+        if self.channels:
+            need = cap * self.channels * self.side * self.side * 4
+            total = torch.cuda.get_device_properties(device).total_memory
+            if need > total // 2:
+                raise ValueError(f"ring planes need {need / 2**30:.1f} GiB ({cap} rows of {self.channels} x {self.side}^2 floats): "
+                                 f"lower the capacity or pass planes=False")
+            self.planes = torch.empty((cap, self.channels, self.side, self.side), dtype=torch.float32, device=device)
+        self.policy = e((cap, self.kmax), torch.float32)
+        self.idx = torch.full((cap, self.kmax), -1, dtype=torch.int32, device=device)
+        self.value = e((cap,), torch.float64)
+        self.reward = e((cap,), torch.float64)
+        self.flags = e((cap,), torch.uint8)
+        self._owner = owner
+        self.draws = 0
+        self.last_offsets = None
+        self.timing = None  # list of (start, end) events around each gather launch while profiling
+
+    def __len__(self) -> int:
+        """Committed rows (reads the device)."""
+        return int((self.flags == COMMITTED).sum().item())
+
+    def committed_rows(self):
+        """Device int64 indices of the committed rows, ascending."""
+        return self.torch.nonzero(self.flags == COMMITTED).reshape(-1)
+
+    def sample(self, batch_size: int, num_augmented_samples: int = 0, check_empty: bool = True):
+        """(states [b (k+1), C, N, N] f32, policies [b (k+1), A] f32, values f64, rewards f64, valid_actions_msk [b (k+1), A] u8,
+        indices i64 (ring rows), weights (ones, f64)) -- ExperienceReplayBuffer.sample with augment_random_crop: b = max(1, batch_size //
+        (k + 1)) rows drawn uniformly with replacement from the committed rows, originals first, then k shifted copies.  states is None
+        without planes.  check_empty reads the committed count from the device and raises on an empty buffer (else the rows are -1 / NaN)."""
+        torch = self.torch
+        k = int(num_augmented_samples)
+        if k < 0:
+            raise ValueError("num_augmented_samples must be >= 0")
+        n = max(1, int(batch_size) // (k + 1))
+        copies = k + 1
+        cum = torch.cumsum((self.flags == COMMITTED).to(torch.int32), 0, dtype=torch.int32)
+        if check_empty and int(cum[-1].item()) == 0:
+            raise ValueError("the replay buffer holds no committed sample yet (no episode has ended)")
+        dev, rows = self.flags.device, n * copies
+        states = torch.empty((rows, self.channels, self.side, self.side), dtype=torch.float32, device=dev) if self.channels else None
+        pol = torch.empty((rows, self.num_actions), dtype=torch.float32, device=dev)
+        msk = torch.empty((rows, self.num_actions), dtype=torch.uint8, device=dev)
+        val = torch.empty((rows,), dtype=torch.float64, device=dev)
+        rew = torch.empty((rows,), dtype=torch.float64, device=dev)
+        index = torch.empty((rows,), dtype=torch.int64, device=dev)
+        offs = torch.empty((copies, 2), dtype=torch.int32, device=dev)
+        own = self._owner
+        if self.timing is not None:  # (events around the gather kernel alone: tools/selfplay_bench.py)
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+        _ffi.check(own._lib.ipp_replay_gather(C.byref(own._sp), n, copies, self.channels, self.side,
+                                              self.planes.data_ptr() if self.channels else None, cum.data_ptr(), C.c_uint64(self.seed),
+                                              C.c_uint64(REPLAY_STREAM + self.draws), states.data_ptr() if states is not None else None,
+                                              pol.data_ptr(), msk.data_ptr(), val.data_ptr(), rew.data_ptr(), index.data_ptr(), offs.data_ptr(),
+                                              own.env.engine.stream))
+        if self.timing is not None:
+            ev[1].record()
+            self.timing.append(ev)
+        self.draws += 1
+        self.last_offsets = offs
+        return states, pol, val, rew, msk, index, torch.ones((rows,), dtype=torch.float64, device=dev)
+
+
+# ---------------------------------------------------------------------------------------------------- the loop
+class SelfPlay:
+    def __init__(self, cfg, num_envs: int, hyper_params: Dict, meta_data: Dict, infer: Optional[Callable] = None,
+                 capacity: Optional[int] = None, seed: int = 0, env_id_offset: int = 0, random_init_action: bool = True,
+                 planes: bool = True, sims_in_flight: int = 4, tie_break: str = "first", groups: int = 2, device: str = "cuda:0",
+                 **env_kwargs):
+        """cfg: EngineConfig; hyper_params / meta_data: the reference's dictionaries (config/example.yaml: gamma, puct_*, dirichlet_*,
+        num_mcts_simulations, temperature_scale / _threshold, input_history_length, use_fov_input, use_action_costs_input, shuffle_budget;
+        initial_budget, max_episode_steps, episode_horizon, min / max_altitude, altitude_spacing, uav_specifications, scenario_info).
+        infer: DeviceMCTS's network callback (None: uniform priors, value 0); with a network the leaves' planes come along.
+        capacity: ring rows (a multiple of num_envs, at least (max_episode_steps + 1) num_envs; default the minimum).
+        planes=False keeps no planes in the ring (large grids: a 50x50 plane is 25 MB per channel).  env_kwargs go to VecIPPEnv."""
+        S, steps = check_args(hyper_params, meta_data, num_envs, capacity)
+        import torch
+
+        from ...feature_planes import PlaneSpec
+        from .device_mcts import DeviceMCTS
+
+        self.torch = torch
+        hp, md = dict(hyper_params), dict(meta_data)
+        md.setdefault("budget", md["initial_budget"])
+        self.hp, self.md = hp, md
+        B = self.num_envs = int(num_envs)
+        self.slots, self.max_episode_steps = S, steps
+        self.seed, self.random_init = int(seed), bool(random_init_action)
+        horizon = int(md["episode_horizon"])
+        sims, W = int(hp["num_mcts_simulations"]), int(sims_in_flight)
+        H = int(hp["input_history_length"])
+        env_kwargs.setdefault("window_rows", -1)
+        env_kwargs.setdefault("adaptive", md.get("scenario_info") is not None)
+        env_kwargs.setdefault("use_flight_time", md.get("uav_specifications") is not None)
+        env_kwargs.setdefault("node_capacity", B * (sims + 16))
+        env_kwargs.setdefault("max_batch", B * W)
+        env_kwargs.setdefault("rank_cap", 9 * (steps + horizon + 2))  # (a search adds up to horizon + 1 steps of columns to a root)
+        self.env = VecIPPEnv(cfg, B, episode_steps=steps, device=device, seed=seed, env_id_offset=env_id_offset,
+                             budget=float(md["initial_budget"]), shuffle_budget=bool(hp.get("shuffle_budget", False)), feature_history=H,
+                             **env_kwargs)
+        env = self.env
+        self.device = env.device
+        self.spec = PlaneSpec.from_params(hp, md, adaptive=env.adaptive, use_flight_time=env.use_flight_time)
+        self.mcts = DeviceMCTS(env.engine, hp, md, infer, sims_in_flight=W, tie_break=tie_break, seed=seed, groups=groups,
+                               feature_planes=infer is not None)
+        self.mcts._key_base = env.env_id_offset  # (the search's counter-based draws keyed on the global env id too)
+        self.infer = infer
+        geo = self.mcts._geometry(torch, self.device)
+        self.kmax, self.num_actions = int(geo["kmax"]), int(self.mcts.num_actions)
+        if self.kmax > MAX_KMAX:
+            env.engine.close()
+            raise ValueError(f"valid-action sets of up to {self.kmax} actions (max_valid_action_distance {hp['max_valid_action_distance']}): "
+                             f"the ring rows hold at most {MAX_KMAX}")
+        self.actions = geo["actions"]
+        # temperatures: temperature_scale * (depth < temperature_threshold) (:118-120); a temperature-0 step takes the arg-max of the
+        # read-out at temperature 1 (visits / sum: same order, same ties)
+        scale, thr = float(hp["temperature_scale"]), int(hp["temperature_threshold"])
+        self.temp_zero = not scale > 0
+        need_pos, need_zero = (not self.temp_zero) and thr > 0, self.temp_zero or thr < steps
+        self._temps = ([scale] if need_pos else []) + ([1.0] if need_zero and not (need_pos and scale == 1.0) else [])
+        self._t_index = (0, len(self._temps) - 1)  # (policy_t, policy_1) among the read-outs
+        self.replay = ReplayBuffer(self, S, B, self.kmax, self.num_actions, self.spec.channels if planes else 0, cfg.n_cells,
+                                   seed, self.device)
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.device)  # noqa: E731
+        self.ep_len, self.forced = z((B,), torch.int32), z((B,), torch.uint8)
+        self.tie_u = z((B,), torch.float64)
+        self.episode_values = torch.full((B,), float("nan"), dtype=torch.float64, device=self.device)
+        self.action, self.action_idx = z((B, 3), torch.float64), z((B,), torch.int32)
+        self._roots = torch.arange(B, dtype=torch.int32, device=self.device)
+        self._lib = env.engine._lib
+        r = self.replay
+        sp = self._sp = _ffi.IppSelfPlay(
+            num_envs=B, slots=S, kmax=self.kmax, num_actions=self.num_actions, horizon=horizon, temp_threshold=thr,
+            temp_zero=int(self.temp_zero), random_init=int(self.random_init), device=self.device.index or 0, reserved=0,
+            gamma=float(hp["gamma"]), seed=self.seed & (2 ** 64 - 1), row_offset=env.env_id_offset)
+        ptrs = dict(actions=self.actions, budget=env.budget, depth=env.depth, episode=env.episode, done=env.done, prev=env.prev,
+                    reward=env.reward, ep_len=self.ep_len, forced=self.forced, tie_u=self.tie_u, episode_value=self.episode_values,
+                    action=self.action, action_idx=self.action_idx, r_policy=r.policy, r_idx=r.idx, r_value=r.value,
+                    r_reward=r.reward, r_flags=r.flags)
+        for name, t in ptrs.items():
+            setattr(sp, name, t.data_ptr())
+        self.t = 0
+        self.last = None
+        self.timing = None  # dict phase -> list of (start, end) event pairs while profiling (tools/selfplay_bench.py)
+        self.reset()
+
+    # ------------------------------------------------------------------
+    def reset(self):
+        """Every env starts episode 0 (the env's reset), at its drawn first waypoint; the ring keeps its committed rows."""
+        torch, env, B = self.torch, self.env, self.num_envs
+        env.reset()
+        gid = np.arange(B, dtype=np.int64) + env.env_id_offset
+        epi = env.episode.cpu().numpy()
+        if self.random_init:
+            a0 = init_action_index(self.seed, gid, epi, self.num_actions)
+            env.prev.copy_(self.actions[torch.as_tensor(a0, device=self.device)])
+        self.tie_u.copy_(torch.as_tensor(step_uniform(TIE_STREAM, self.seed, gid, epi, env.depth.cpu().numpy()), device=self.device))
+        self.ep_len.zero_()
+        self.forced.zero_()
+        self.replay.flags[self.replay.flags == PENDING] = 0  # (rows of episodes that will never end)
+
+    def _mark(self, name):
+        if self.timing is not None:
+            ev = self.torch.cuda.Event(enable_timing=True)
+            ev.record()
+            self.timing.setdefault(name, []).append(ev)
+
+    def step(self):
+        """One search per env, record, sample the actions, env.step, commit the episodes that ended.  episode_values: the
+        total_episode_value of every env whose episode ended in this step (NaN elsewhere)."""
+        env, r, B = self.env, self.replay, self.num_envs
+        t = self.t
+        slot = t % self.slots
+        self._mark("planes")
+        ent = env.history_entries() if (r.channels or self.infer is not None) else None
+        if r.channels:  # (= env.feature_planes(spec, out=...): the same entries feed the search's leaf planes)
+            env.engine.feature_planes(ent, self.spec, mask_env=ent[:, 0, 0], out=r.planes[slot * B:(slot + 1) * B])
+        self._mark("search")
+        out = self.mcts.search_device(self._roots, env.prev, env.budget, self._temps, self.tie_u, depth=0,
+                                      root_history=ent if self.infer is not None else None)
+        pol_t, pol_1 = out["policy"][self._t_index[0]], out["policy"][self._t_index[1]]
+        self.last = dict(policy_t=pol_t, policy_1=pol_1, valid_idx=out["valid_idx"], ok=out["ok"])
+        self._mark("record")
+        _ffi.check(self._lib.ipp_selfplay_record(C.byref(self._sp), int(t), pol_t.data_ptr(), pol_1.data_ptr(), out["valid_idx"].data_ptr(),
+                                                 out["ok"].data_ptr(), env.engine.stream))
+        self._mark("step")
+        env.step(self.action)
+        self._mark("commit")
+        _ffi.check(self._lib.ipp_selfplay_commit(C.byref(self._sp), int(t), env.engine.stream))
+        self._mark("end")
+        self.t += 1
+        return self.episode_values
+
+    def run(self, steps: int):
+        for _ in range(int(steps)):
+            self.step()
+        return self
+
+    def close(self):
+        self.env.engine.close()

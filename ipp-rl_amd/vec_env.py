@@ -93,13 +93,16 @@ class VecIPPEnv:
                  device: str = "cuda:0", seed: int = 1234, env_id_offset: int = 0, shuffle_prior_cov: bool = False,
                  rank_cap: Optional[int] = None, stagger: bool = False, tile_threads: int = 0,
                  adaptive: bool = True, use_flight_time: bool = True, window_rows: int = 0, fused_reset: bool = True,
-                 parts: int = 1, arena=None, budget: Optional[float] = None, shuffle_budget: bool = False, feature_history: int = 0):
+                 parts: int = 1, arena=None, budget: Optional[float] = None, shuffle_budget: bool = False, feature_history: int = 0,
+                 node_capacity: int = 0, max_batch: Optional[int] = None):
         """budget=None: episodes of exactly `episode_steps` steps on a schedule known to the host.  budget=B0: the reference's
         budget-driven episodes (planning/mcts_zero/episode_generators.py:109-150) -- `episode_steps` is max_episode_steps, every env
         carries a device-side ledger (self.budget, self.depth, self.episode, self.done) that the step kernel charges with the action
         cost, and an env whose loop condition fails is reset inside the step launch; its next ground truth is generated behind
         the step from the device's refill list (no device->host sync in the loop).  shuffle_budget: start budgets
-        floor(U(10, B0)) per env and episode (start_budget)."""
+        floor(U(10, B0)) per env and episode (start_budget).  node_capacity / max_batch: the engine's tree nodes and largest launch
+        (IPPEngine), for a search whose roots are the env slots (planning/mcts_zero/selfplay.py); the defaults build no nodes and launches of
+        num_envs items."""
         import torch
 
         self.torch = torch
@@ -134,7 +137,7 @@ class VecIPPEnv:
         rank_cap = int(rank_cap) if rank_cap else 9 * self.episode_steps
         self.engine = IPPEngine(cfg, capacity=self.num_envs, state=state, rank_cap=rank_cap, device=device,
                                 tile_threads=tile_threads, window_rows=window_rows, fixed_prior=not shuffle_prior_cov,
-                                arena=arena)
+                                arena=arena, node_capacity=int(node_capacity), max_batch=max_batch)
         if self.budget_mode and (int(self.engine.info.patch_layout) != 1 or int(self.engine.info.fused_step) != 1):
             self.engine.close()
             raise ValueError("budget mode: patch-layout engines only (windowed factor state, ipp_info.patch_layout == 1)")

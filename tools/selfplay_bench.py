@@ -1,0 +1,97 @@
+"""
+Throughput of the batched self-play loop (planning/mcts_zero/selfplay.py): samples/s and the split of a step into its phases --
+planes (ipp_feature_planes into the ring), search (DeviceMCTS, read-out on the device), record (ipp_selfplay_record), step (the fused
+budget step), commit (ipp_selfplay_commit) -- plus one replay minibatch (gather, ipp_replay_gather), from CUDA events around each phase.
+
+    python tools/selfplay_bench.py [--envs 4096] [--dim 50] [--sims 100] [--steps 8] [--warmup 2] [--planes-envs 8]
+
+The 4096-env run keeps no planes (a 50x50 plane is 25 MB per channel): its planes phase is reported as not measured; the planes phase
+and the gather kernel (CUDA events around the ipp_replay_gather launch alone, one minibatch of --batch rows with one augmented copy) are
+timed on a second, small batch (--planes-envs) with planes in its ring.  Prints one JSON line.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def params(sims, steps):
+    hp = dict(gamma=1.0, puct_init=15.0, puct_base=10000.0, forced_playout_factor=2.0, max_valid_action_distance=11.5, dirichlet_alpha=1.0,
+              dirichlet_eps=0.25, num_mcts_simulations=sims, temperature_scale=1.0, temperature_threshold=40, input_history_length=3,
+              use_fov_input=False, use_action_costs_input=True, reset_mcts_each_step=True, use_per=False, shuffle_prior_cov=False,
+              shuffle_budget=False)
+    md = dict(initial_budget=200.0, max_episode_steps=steps, episode_horizon=5, min_altitude=8.0, max_altitude=14.0, altitude_spacing=6.0,
+              uav_specifications={"max_v": 2.0, "max_a": 2.0}, scenario_info={"value_threshold": 0.4, "interval_factor": 0})
+    return hp, md
+
+
+def timed(sp, steps):
+    import torch
+
+    sp.timing = {}
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        sp.step()
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t0
+    ev = sp.timing
+    sp.timing = None
+    order = ["planes", "search", "record", "step", "commit", "end"]
+    split = {}
+    for a, b in zip(order[:-1], order[1:]):
+        split[a] = sum(s.elapsed_time(e) for s, e in zip(ev[a], ev[b])) / steps
+    return wall, split
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--dim", type=int, default=50)
+    ap.add_argument("--sims", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=8)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--episode-steps", type=int, default=40)
+    ap.add_argument("--planes-envs", type=int, default=8)
+    ap.add_argument("--batch", type=int, default=96)
+    a = ap.parse_args()
+    import torch
+
+    from ipp_rl_amd import EngineConfig
+    from ipp_rl_amd.planning.mcts_zero import SelfPlay
+
+    cfg = EngineConfig(x_dim=a.dim, y_dim=a.dim)
+    hp, md = params(a.sims, a.episode_steps)
+    sp = SelfPlay(cfg, a.envs, hp, md, planes=False, seed=1)
+    sp.run(a.warmup)
+    wall, split = timed(sp, a.steps)
+    ended = int((~torch.isnan(sp.episode_values)).sum().item())
+    with_policy = int(sp.last["ok"].sum().item())
+    sp.close()
+    del sp
+    # the planes phase with planes in the ring (small batch, history 3, cost plane: 16 channels) and 3-step episodes, so that rows are
+    # committed and one minibatch with one augmented copy is gathered (ipp_replay_gather)
+    hp3, md3 = params(a.sims, 3)
+    small = SelfPlay(cfg, a.planes_envs, hp3, md3, planes=True, seed=1)
+    small.run(1)
+    _, split_small = timed(small, 3)
+    small.replay.timing = []
+    batch = small.replay.sample(a.batch, num_augmented_samples=1, check_empty=False)
+    torch.cuda.synchronize()
+    gather_ms = small.replay.timing[0][0].elapsed_time(small.replay.timing[0][1])  # (the ipp_replay_gather kernel alone)
+    small.replay.timing = None
+    gathered_rows = int((batch[5] >= 0).sum().item())
+    small.close()
+    split["planes"] = "not measured: the 4096-env batch keeps no planes (planes=False); see planes_ms_small_batch"
+    out = {"envs": a.envs, "grid": a.dim, "sims": a.sims, "steps": a.steps, "samples_per_s": a.envs * a.steps / wall,
+           "step_ms": 1e3 * wall / a.steps, "split_ms": split, "episodes_ended_last_step": ended,
+           "roots_with_policy_last_step": with_policy, "gather_kernel_ms_small_batch": gather_ms, "gathered_rows": gathered_rows,
+           "planes_ms_small_batch": {"envs": a.planes_envs, "planes": split_small["planes"], "record": split_small["record"]}}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

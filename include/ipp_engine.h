@@ -314,6 +314,33 @@ int ipp_set_budget(void* engine, double* budget, int32_t* depth, int64_t* episod
 int ipp_score_actions(void* engine, int32_t env_id, const double* actions, int32_t n, const double* prev_action,
                       uint32_t flags, float* reward, int32_t* status, void* stream);
 
+/*
+ * Reward of k candidate actions from the CURRENT state of EACH of n env slots, in one call; nothing is written to any
+ * env.  Per (env, candidate) exactly the reward of ipp_step(IPP_COV_ONLY | IPP_PREDICT_ONLY) for that env and action:
+ * the adaptive mask comes from the env's own mean and diagonal (planning/common/rewards.py:8-31), the numerator is
+ * divided by cost + 1.  The batched greedy planner's call (planning/common/optimization.py:33-104 for every env of a
+ * batch).  The call builds the item lists on the device (csrc/k_score_batch.h) and runs the predict-only step
+ * launches itself, max_batch items at a time: n x k is not bound by max_batch.
+ * Engines: the patch-layout windowed factor engine only (ipp_info.patch_layout == 1); every other engine returns an
+ * error.
+ *   env_ids     [dev]  int32[n] or NULL (= 0..n-1); repeats are allowed
+ *   actions     [dev]  double[n][k][3]; a row with a non-finite entry = no candidate: reward 0, cost NaN,
+ *                      IPP_STATUS_BAD_FOOTPRINT (a footprint above the compiled caps: the same status, reward 0)
+ *   prev_action [dev]  double[n][3]      the waypoint the candidates of item i start from
+ *   flags              IPP_ADAPTIVE | IPP_USE_FLIGHT_TIME
+ *   reward      [dev]  float[n][k]
+ *   cost        [dev]  double[n][k] or NULL: the action cost (planning/common/actions.py:8-41), for the budget filter
+ *                      0 < cost <= remaining budget of get_actions (actions.py:63)
+ *   status      [dev]  int32[n][k] or NULL
+ *   scratch     [dev]  caller-owned, at least ipp_score_actions_envs_scratch_bytes(engine, n, k) bytes: per candidate
+ *                      its env id and start waypoint (28 bytes)
+ */
+int ipp_score_actions_envs(void* engine, const int32_t* env_ids, int32_t n, int32_t k, const double* actions,
+                           const double* prev_action, uint32_t flags, float* reward, double* cost, int32_t* status,
+                           void* scratch, uint64_t scratch_bytes, void* stream);
+/* bytes of caller-owned scratch a call of ipp_score_actions_envs with n x k candidates needs ([host] out) */
+int ipp_score_actions_envs_scratch_bytes(void* engine, int32_t n, int32_t k, uint64_t* bytes);
+
 #define IPP_TREE_DEPTH 6 /* nodes on a path of ipp_tree_step */
 
 /*

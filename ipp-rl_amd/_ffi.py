@@ -132,6 +132,8 @@ PROTOTYPES = {
     "ipp_reset": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
     "ipp_reset_episode": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "ipp_score_actions": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_uint32, _P, _P, _P]),
+    "ipp_score_actions_envs": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, C.c_uint32, _P, _P, _P, _P, C.c_uint64, _P]),
+    "ipp_score_actions_envs_scratch_bytes": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]),
     "ipp_state_plane": (C.c_int, [_P, C.c_int32, _P, C.c_uint32, _P, _P]),
     "ipp_feature_planes": (C.c_int, [_P, C.POINTER(IppPlaneSpec), _P, C.c_int32, _P, _P, _P, _P]),
     "ipp_mcts_plane_entries": (C.c_int, [C.POINTER(IppMctsTables), _P, _P, _P, _P, C.c_int32, C.c_double, C.c_int32, _P, _P, _P]),

@@ -26,6 +26,7 @@
 #include "k_grf_fft.h"
 #include "k_fields.h"
 #include "k_score.h"
+#include "k_score_batch.h"
 #include "k_plane.h"
 #include "k_feature_planes.h"
 #include "k_tree.h"
@@ -1892,6 +1893,51 @@ int ipp_replay_gather(const ipp_selfplay* sp, int32_t n, int32_t copies, int32_t
 int ipp_score_actions(void* engine, int32_t env_id, const double* actions, int32_t n, const double* prev_action,
                       uint32_t flags, float* reward, int32_t* status, void* stream) {
     return score_actions_impl(engine, env_id, ScorePath{}, nullptr, actions, n, prev_action, flags, reward, status, stream);
+}
+
+// ipp_score_actions_envs (k_score_batch.h): the item lists of the predict-only step launches live in the caller's scratch
+int ipp_score_actions_envs_scratch_bytes(void* engine, int32_t n, int32_t k, uint64_t* bytes) {
+    Engine* e = as_engine(engine);
+    if (!e || !bytes) return fail(-1, "null argument");
+    if (n < 0 || k < 0) return fail(-1, "n = %d, k = %d: negative", n, k);
+    if (!e->patch) return fail(-1, "ipp_score_actions_envs needs the patch-layout windowed factor engine (ipp_info.patch_layout == 1)");
+    *bytes = score_batch_scratch_bytes((uint64_t)n * (uint64_t)k);
+    return 0;
+}
+
+int ipp_score_actions_envs(void* engine, const int32_t* env_ids, int32_t n, int32_t k, const double* actions,
+                           const double* prev_action, uint32_t flags, float* reward, double* cost, int32_t* status,
+                           void* scratch, uint64_t scratch_bytes, void* stream) {
+    Engine* e = as_engine(engine);
+    if (!e || !actions || !prev_action || !reward) return fail(-1, "null argument");
+    if (!e->patch) return fail(-1, "ipp_score_actions_envs needs the patch-layout windowed factor engine (ipp_info.patch_layout == 1)");
+    if (n < 0 || k < 0) return fail(-1, "n = %d, k = %d: negative", n, k);
+    if (flags & ~(IPP_COV_ONLY | IPP_PREDICT_ONLY | IPP_ADAPTIVE | IPP_USE_FLIGHT_TIME)) return fail(-1, "unsupported flag bits 0x%x", flags);
+    const uint64_t items = (uint64_t)n * (uint64_t)k;
+    const uint64_t need = score_batch_scratch_bytes(items);
+    if (items == 0) return 0;
+    if (scratch_bytes < need || !scratch)
+        return fail(-1, "scratch of %llu bytes, ipp_score_actions_envs needs %llu for n = %d, k = %d", (unsigned long long)scratch_bytes,
+                    (unsigned long long)need, n, k);
+    if ((items + 255) / 256 > 0x7fffffffull) return fail(-1, "n x k = %llu candidates exceed one call", (unsigned long long)items);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(e->device));
+    int* ids = reinterpret_cast<int*>(scratch);
+    double* prevx = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(scratch) + score_batch_ids_bytes(items));
+    hipLaunchKernelGGL(k_score_expand, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, e->v, env_ids, n, k, actions, prev_action, flags,
+                       ids, prevx, cost);
+    HIP_TRY(hipGetLastError());
+    // one predict-only covariance-only item per candidate, in launches of at most max_batch items: the candidates of an env are
+    // consecutive items, so its columns stay in the caches between them
+    const uint32_t step_flags = (flags & (IPP_ADAPTIVE | IPP_USE_FLIGHT_TIME)) | IPP_COV_ONLY | IPP_PREDICT_ONLY;
+    const uint64_t mb = (uint64_t)e->v.max_batch;
+    for (uint64_t o = 0; o < items; o += mb) {
+        const int cnt = (int)std::min<uint64_t>(mb, items - o);
+        if (int rc = ipp_step(engine, ids + o, nullptr, cnt, actions + 3 * o, prevx + 3 * o, nullptr, step_flags, reward + o,
+                              status ? status + o : nullptr, stream))
+            return rc;
+    }
+    return 0;
 }
 
 int ipp_tree_score_actions(void* engine, int32_t root_id, const int32_t* path_ids, const double* actions, int32_t n,

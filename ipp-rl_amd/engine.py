@@ -403,6 +403,40 @@ class IPPEngine:
         self._keep_score = a
         return reward, status
 
+    def score_actions_envs(self, actions, prev, env_ids=None, *, adaptive=True, use_flight_time=True, want_cost=False):
+        """Reward of k candidate actions from the current state of each of n env slots in one call (ipp_score_actions_envs;
+        patch-layout engines): actions [n, k, 3] (a NaN row = no candidate), prev [n, 3], env_ids [n] or None (= 0..n-1).
+        Returns (reward [n, k] float32, status [n, k] int32[, cost [n, k] float64]); nothing is written to any env and nothing
+        is read back to the host.  One scratch tensor per (n, k) shape (the call's item lists) stays alive between calls."""
+        torch = _torch()
+        a = self._dev(actions, torch.float64)
+        if a.dim() != 3 or a.shape[2] != 3:
+            raise ValueError("actions must be [n, k, 3]")
+        n, k = int(a.shape[0]), int(a.shape[1])
+        p = self._dev(prev, torch.float64).reshape(-1, 3)
+        if p.shape[0] != n:
+            raise ValueError("prev must be [n, 3]")
+        ids = self._dev(env_ids, torch.int32)
+        if ids is not None and ids.numel() != n:
+            raise ValueError("env_ids must have one entry per row of actions")
+        if ids is None and n > self.capacity:
+            raise ValueError(f"n = {n} envs without env_ids, capacity {self.capacity}")
+        cache = self.__dict__.setdefault("_score_envs_scratch", {})
+        scratch = cache.get((n, k))
+        if scratch is None:
+            nbytes = C.c_uint64(0)
+            _ffi.check(self._lib.ipp_score_actions_envs_scratch_bytes(self._h, n, k, C.byref(nbytes)))
+            scratch = cache[(n, k)] = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
+        reward = torch.empty((n, k), dtype=torch.float32, device=self.device)
+        status = torch.empty((n, k), dtype=torch.int32, device=self.device)
+        cost = torch.empty((n, k), dtype=torch.float64, device=self.device) if want_cost else None
+        flags = (_ffi.IPP_ADAPTIVE if adaptive else 0) | (_ffi.IPP_USE_FLIGHT_TIME if use_flight_time else 0)
+        _ffi.check(self._lib.ipp_score_actions_envs(self._h, self._ptr(ids), n, k, self._ptr(a), self._ptr(p), flags, self._ptr(reward),
+                                                    self._ptr(cost), self._ptr(status), self._ptr(scratch) if scratch.numel() else None,
+                                                    int(scratch.numel()), self.stream))
+        self._keep_score = (a, p, ids)
+        return (reward, status, cost) if want_cost else (reward, status)
+
     TREE_DEPTH = 6
 
     def tree_step(self, root_ids, path_ids, actions, prev_actions, new_ids=None, *, adaptive=True, use_flight_time=True,

@@ -1,0 +1,1 @@
+from .vec_greedy import VecGreedyPolicy  # noqa: F401

@@ -86,6 +86,11 @@ def cell_centre_actions(cfg: EngineConfig, step: int, env_lo: int, env_hi: int, 
     return acts[env_lo:env_hi]
 
 
+def torch_index(torch, ids, device):
+    """int64 device index tensor from a tensor / array / list of env ids."""
+    return ids.to(device=device, dtype=torch.int64) if isinstance(ids, torch.Tensor) else torch.as_tensor(np.asarray(ids), dtype=torch.int64, device=device)
+
+
 class VecIPPEnv:
     NOISE_RING = 16
 
@@ -411,6 +416,13 @@ class VecIPPEnv:
             raise ValueError(f"spec.history = {spec.history} != feature_history = {self.feature_history}")
         ent = self.history_entries(env_ids)
         return self.engine.feature_planes(ent, spec, mask_env=ent[:, 0, 0], out=out)
+
+    def score_actions(self, actions, env_ids=None, want_cost=False):
+        """Reward of k candidate waypoints per env from the envs' current states and waypoints (IPPEngine.score_actions_envs with
+        prev = self.prev): actions [n, k, 3], a NaN row = no candidate.  Nothing is written, nothing is read back to the host."""
+        prev = self.prev if env_ids is None else self.prev[torch_index(self.torch, env_ids, self.device)]
+        return self.engine.score_actions_envs(actions, prev, env_ids=env_ids, adaptive=self.adaptive, use_flight_time=self.use_flight_time,
+                                              want_cost=want_cost)
 
     def _step_budget(self, actions, meas_noise, auto_reset: bool):
         """One budget-mode step of the whole batch (parts == 1): the ledger is charged in the step launch, the envs it ends reset there

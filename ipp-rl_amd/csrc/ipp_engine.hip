@@ -34,6 +34,7 @@
 #include "k_mcts.h"
 #include "k_selfplay.h"
 #include "k_prepare.h"
+#include "patch_launch.h"
 
 using namespace ipp;
 
@@ -67,10 +68,6 @@ namespace {
 constexpr uint64_t kAlign = 256;
 constexpr int kMaxChunks = 8;
 inline uint64_t up(uint64_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
-
-#ifndef IPP_PATCH_BIGKP
-#define IPP_PATCH_BIGKP 4  // rows per request group of the six-waves-per-SIMD instantiation of k_step_patch
-#endif
 
 struct ProfEvent { hipEvent_t a, b; int kind; };
 constexpr int kProfKinds = 4;  // 0 streaming kernel, 1 dense downdate, 2 prologue kernel; 3: every launch of a step (busy time only)
@@ -106,17 +103,7 @@ struct Engine {
     bool tree_ok = false; // ipp_tree_step available (fused engines; MC = 25: the fused tree kernel beside two-launch env steps)
     size_t tree_fused_lds = 0;
     bool patch = false;   // k_step_patch on compact column patches (View::patch)
-    int patch_waves = kPatchWavesDefault;  // waves per item of k_step_patch
-    int split_min_items = 0;  // launches of at least this many items run the SPLIT step (k_step_split.h: prologue kernel + unit kernel); 0: never
-    int split_waves = 3;      // waves per item of its prologue kernel
-    int pcap_p = 0;           // records the prologue kernel of the split step stages in LDS (a multiple of 8)
-    size_t lds_p = 0, lds_u = 0;
-    int pcap_big = 0, big_min_items = 0;  // large launches: k_step_patch<2, 4, 6> with LDS for 12 workgroups per CU (0: never)
-    size_t lds_big = 0;
-    // three-wave engines (the default): launches of at least two_wave_min_items items run TWO waves per item (k_step_patch<2>, 12 items
-    // per CU = 3072 slots; from big_min_items its four-rows-per-group form) -- 0: never
-    int pcap2 = 0, two_wave_min_items = 0;
-    size_t lds2 = 0;
+    PatchPlan pp;         // ... which instantiation a launch runs, its record capacity and LDS (patch_launch.h)
     const double* reset_prior = nullptr;  // ipp_set_reset_prior: priors of the episodes started by ipp_step_autoreset
     Ledger led = {};                      // ipp_set_budget: the budget ledger of IPP_BUDGET steps (budget == NULL: none installed)
     bool rect_ok = false;      // rectangle tiles (k_gain_factor.h) possible: clipped windows, 128-cell tiles, even grid width
@@ -138,7 +125,6 @@ struct Engine {
 struct Layout {
     int N, Npad, T, n_tiles, win_tiles, MC, FC, QS, q_rows, VEC;
     bool patch;
-    int patch_waves;
     PatchGeo pg;
     uint64_t off_mean, off_diag, off_gt, off_gtslot, off_prior, off_rank, off_span, off_cnt, off_icnt, off_cov, off_blk, off_hdr, off_linv, off_yv, off_q, off_wc,
         off_partial, off_dbg, off_grfh, off_grfcs, off_grfg, off_grfhp, off_grfamp, off_grfraw, off_grfraw2, off_sc_hdr, off_sc_ext, off_sc_mask, off_sc_G, off_sc_P, off_tr_cov, off_tr_diag, off_tr_meta, off_sc_ndiag, total, cov_slot_floats;
@@ -154,14 +140,9 @@ uint64_t q_item_floats(const Layout& L) {
 
 // Compact column patches + k_step_patch / k_tree_patch (k_step_patch.h, k_tree_patch.h): windowed factor engines on grids wide enough for two-dimensional windows, MC = 9.  Any of the A/B
 // switches of the band-tile kernels selects those kernels instead; IPP_PATCH=0 does so explicitly.
-bool patch_layout(const ipp_config& c, int MC) {
+bool patch_layout(const ipp_config& c, int MC, const Switches& sw) {
     if (c.state_repr != IPP_FACTOR || c.window_rows <= 0 || MC != 9) return false;
     if (c.tile_threads != 0) return false;
-    if (c.node_capacity > 0) {
-        // tree nodes on patches (k_tree_patch.h): the records address column patches by 32-bit offsets in 8-byte units from
-        // View::cov: root slots + node blocks must lie within 32 GB of it
-        // (plan() checks the reach of the 32-bit record offsets on the finished layout)
-    }
     if (c.x_dim % 2 != 0 || c.x_dim > 256 || c.y_dim > 256) return false;
     if (!(c.x_dim > 2 * c.window_rows + 13)) return false;
     if (c.rank_cap > kPatchMaxRank) return false;
@@ -170,14 +151,8 @@ bool patch_layout(const ipp_config& c, int MC) {
         const PatchGeo g = patch_geometry(c.x_dim, c.y_dim, c.window_rows);
         if (!patch_units_exact(g.pw, g.ph)) return false;
     }
-    for (const char* name : {"IPP_RECT_META", "IPP_RECT", "IPP_FUSED", "IPP_STEP_CHUNKS"})
-        if (getenv(name)) return false;
-    if (const char* p = getenv("IPP_PATCH")) return atoi(p) != 0;
-    return true;
-}
-int patch_waves_wanted() {
-    if (const char* w = getenv("IPP_PATCH_WAVES")) { const int n = atoi(w); if (n >= 1 && n <= 4) return n; }
-    return kPatchWavesDefault;
+    if (sw.rect_meta || sw.rect || sw.fused || sw.step_chunks) return false;
+    return !sw.patch || *sw.patch != 0;
 }
 
 // Windowed factor columns: the largest length scale a reset may install and the prior covariance dropped at the
@@ -213,7 +188,7 @@ int min_window_rows(const ipp_config& c, int kind) {
     return r;
 }
 
-int plan(const ipp_config& c, int kind, Layout& L, bool allow_patch = true) {
+int plan(const ipp_config& c, int kind, const Switches& sw, Layout& L, bool allow_patch = true) {
     if (!prior_kind_ok(kind)) return fail(-1, "unknown prior kind %d (IPP_PRIOR_MATERN32 / MATERN12 / MATERN52 / RBF)", kind);
     if (c.x_dim <= 0 || c.y_dim <= 0) return fail(-1, "x_dim/y_dim must be positive");
     if (!(c.resolution > 0)) return fail(-1, "resolution must be positive");
@@ -235,8 +210,7 @@ int plan(const ipp_config& c, int kind, Layout& L, bool allow_patch = true) {
     const bool windowed = c.state_repr == IPP_FACTOR && c.window_rows > 0;
     const long window_cells = std::min<long>(c.y_dim, 2L * c.window_rows + 5) * c.x_dim;
     L.VEC = (L.MC == 9 && !(windowed && window_cells < 16 * 256)) ? 4 : 2;
-    L.patch = allow_patch && patch_layout(c, L.MC);
-    L.patch_waves = patch_waves_wanted();
+    L.patch = allow_patch && patch_layout(c, L.MC, sw);
     if (L.patch) {
         L.VEC = 2;
         L.pg = patch_geometry(c.x_dim, c.y_dim, c.window_rows);
@@ -281,7 +255,7 @@ int plan(const ipp_config& c, int kind, Layout& L, bool allow_patch = true) {
         // (Since the rectangle metadata the fused kernel is ahead up to 16384 envs of 50x50 -- 8192: 24.7 vs 23.4 M, 16384:
         // 26.0 vs 23.7 M env-steps/s -- and the split path from 32768: 28.3 vs 26.9 M; on 100x100 the split path stays 23 % ahead.)
         if (c.tile_threads <= 0 && c.node_capacity <= 0 && c.capacity >= ((int64_t)c.x_dim * c.y_dim >= 6000 ? 8192 : 24576)) L.T = 128;
-        if (L.patch) L.T = 64 * L.patch_waves;  // one fused kernel for every batch size
+        if (L.patch) L.T = 64 * sw.patch_waves;  // one fused kernel for every batch size
         if (L.T > 512) return fail(-1, "tile_threads must be <= 512 for IPP_FACTOR");
         L.n_tiles = (n4 + 63) / 64;
         L.Npad = L.n_tiles * 64 * L.VEC;
@@ -347,12 +321,12 @@ int plan(const ipp_config& c, int kind, Layout& L, bool allow_patch = true) {
         L.off_tr_meta = o; o += up(nc * kNodeMeta * 4);
         L.off_sc_ndiag = o; o += c.score_scratch ? up(np * 4) : 0;
         // tree nodes on patches (k_tree_patch.h): a record addresses its column patch by a 32-bit offset in 8-byte units from
-        // View::cov - kTreePatchGuard, so root slots AND node blocks have to lie within 2^35 bytes of it -- decided on the finished
+        // View::cov - kTreePatchGuard, so root slots AND node blocks have to lie within 2^35 bytes (32 GB) of it -- decided on the finished
         // layout (the score scratch sits between the two regions: 6.5 GB at 200x200, 17 GB at 256x256); beyond that the band-tile
         // tree kernels take over
         if (L.patch && allow_patch) {
             const uint64_t reach = (L.off_tr_diag - L.off_cov) + (uint64_t)kTreePatchGuard + (1ull << 20);  // (+ the largest shift of a patch)
-            if (reach >= (1ull << 35)) return plan(c, kind, L, false);
+            if (reach >= (1ull << 35)) return plan(c, kind, sw, L, false);
         }
     }
     L.total = o;
@@ -475,6 +449,38 @@ size_t gain_lds_bytes(const View& v, int q_chunk, int lut_cap) {
     return (b + 15) & ~(size_t)15;
 }
 
+// The instantiations of k_step_patch -- X(NW, KPN, MINW, SPLIT, RJN, an IPP_BUDGET form exists) -- and of k_tree_patch -- X(NW, RJN):
+// the launches and the LDS opt-in of engine creation both go through these lists.
+#define IPP_STEP_PATCH_KERNELS(X)                    \
+    X(1, kPatchKP, kPatchMinW, false, 0, false)      \
+    X(2, kPatchKP, kPatchMinW, false, 0, true)       \
+    X(3, kPatchKP, kPatchMinW, false, 0, true)       \
+    X(3, kPatchKP, kPatchMinW, false, 1, true)       \
+    X(3, kPatchKP, kPatchMinW, false, 2, true)       \
+    X(4, kPatchKP, kPatchMinW, false, 0, false)      \
+    X(2, IPP_PATCH_BIGKP, 6, false, 0, true)         \
+    X(1, kPatchKP, kSplitMinWP, true, 0, false)      \
+    X(2, kPatchKP, kSplitMinWP, true, 0, false)      \
+    X(3, kPatchKP, kSplitMinWP, true, 0, false)
+#define IPP_TREE_PATCH_KERNELS(X) X(2, 0) X(3, 0) X(3, 1) X(4, 0)
+
+using StepPatchKernel = decltype(&k_step_patch<1>);
+using TreePatchKernel = decltype(&k_tree_patch<2>);
+template <bool BUD>
+StepPatchKernel patch_kernel(const PatchVariant& pv) {  // nullptr: not instantiated
+#define X(NW, KPN, MINW, SPLIT, RJN, HASBUD) \
+    if ((HASBUD || !BUD) && pv.waves == NW && pv.kpn == KPN && pv.minw == MINW && pv.split == SPLIT && pv.rjn == RJN) return k_step_patch<NW, KPN, MINW, SPLIT, RJN, BUD && HASBUD>;
+    IPP_STEP_PATCH_KERNELS(X)
+#undef X
+    return nullptr;
+}
+TreePatchKernel tree_patch_kernel(const PatchVariant& pv) {
+#define X(NW, RJN) if (pv.waves == NW && pv.rjn == RJN) return k_tree_patch<NW, RJN>;
+    IPP_TREE_PATCH_KERNELS(X)
+#undef X
+    return nullptr;
+}
+
 // One chunk of items: prologue -> streaming gain (-> reward finalize) (-> dense downdate) on stream `s`.
 // `v` carries scratch pointers already offset to the chunk's first item.
 template <int MC, int VEC>
@@ -483,58 +489,15 @@ void launch_chunk(Engine* e, const View& v, const int32_t* env_ids, const int32_
                   hipEvent_t prep_done, const AutoReset& ar) {
     if (e->patch) {  // compact column patches: one fused kernel, one small workgroup per item (k_step_patch.h)
         if constexpr (MC == 9 && VEC == 2) {
-            if (flags & IPP_BUDGET) {
-                // the budget ledger: the IPP_BUDGET instantiations of the fused kernels the launch would run otherwise (budget_launch_error
-                // has refused the split step and the one- / four-wave A/B engines)
-                if (e->patch_waves == 3 && !(e->two_wave_min_items > 0 && n >= e->two_wave_min_items)) {
-                    if (v.rank_cap <= 192)
-                        timed_launch(e, 0, k_step_patch<3, kPatchKP, kPatchMinW, false, 1, true>, dim3(n), dim3(192), e->gain_lds, s, v, env_ids, n, action, prev, noise, flags, status, reward, ar);
-                    else if (v.rank_cap <= 384)
-                        timed_launch(e, 0, k_step_patch<3, kPatchKP, kPatchMinW, false, 2, true>, dim3(n), dim3(192), e->gain_lds, s, v, env_ids, n, action, prev, noise, flags, status, reward, ar);
-                    else
-                        timed_launch(e, 0, k_step_patch<3, kPatchKP, kPatchMinW, false, 0, true>, dim3(n), dim3(192), e->gain_lds, s, v, env_ids, n, action, prev, noise, flags, status, reward, ar);
-                } else if (e->big_min_items > 0 && n >= e->big_min_items) {
-                    View vb = v;
-                    vb.pcap = e->pcap_big;
-                    timed_launch(e, 0, k_step_patch<2, IPP_PATCH_BIGKP, 6, false, 0, true>, dim3(n), dim3(128), e->lds_big, s, vb, env_ids, n, action, prev, noise, flags, status, reward, ar);
-                } else {
-                    View v2 = v;
-                    if (e->patch_waves == 3) v2.pcap = e->pcap2;
-                    timed_launch(e, 0, k_step_patch<2, kPatchKP, kPatchMinW, false, 0, true>, dim3(n), dim3(128), e->patch_waves == 3 ? e->lds2 : e->gain_lds, s, v2, env_ids,
-                                 n, action, prev, noise, flags, status, reward, ar);
-                }
-            } else if (e->split_min_items > 0 && n >= e->split_min_items) {
-                // split step (k_step_split.h): item-parallel prologue kernel, then one wave per (item, unit)
-                View vp = v;
-                vp.pcap = e->pcap_p;
-                if (e->split_waves == 1)
-                    timed_launch(e, 2, k_step_patch<1, kPatchKP, kSplitMinWP, true>, dim3(n), dim3(64), e->lds_p, s, vp, env_ids, n, action, prev, noise, flags, status, reward, ar);
-                else if (e->split_waves == 2)
-                    timed_launch(e, 2, k_step_patch<2, kPatchKP, kSplitMinWP, true>, dim3(n), dim3(128), e->lds_p, s, vp, env_ids, n, action, prev, noise, flags, status, reward, ar);
-                else
-                    timed_launch(e, 2, k_step_patch<3, kPatchKP, kSplitMinWP, true>, dim3(n), dim3(192), e->lds_p, s, vp, env_ids, n, action, prev, noise, flags, status, reward, ar);
-                timed_launch(e, 0, k_step_units<>, dim3(split_grid(n, v.punits)), dim3(64), e->lds_u, s, v, n, flags, reward, ar);
-            } else if (e->patch_waves == 1)
-                timed_launch(e, 0, k_step_patch<1>, dim3(n), dim3(64), e->gain_lds, s, v, env_ids, n, action, prev, noise, flags, status, reward, ar);
-            else if (e->patch_waves == 4)
-                timed_launch(e, 0, k_step_patch<4>, dim3(n), dim3(256), e->gain_lds, s, v, env_ids, n, action, prev, noise, flags, status, reward, ar);
-            else if (e->patch_waves == 3 && !(e->two_wave_min_items > 0 && n >= e->two_wave_min_items))
-                if (v.rank_cap <= 192)       // (rounds of 192 threads over the columns' rectangles: k_step_patch.h, RJN)
-                    timed_launch(e, 0, k_step_patch<3, kPatchKP, kPatchMinW, false, 1>, dim3(n), dim3(192), e->gain_lds, s, v, env_ids, n, action, prev, noise, flags, status, reward, ar);
-                else if (v.rank_cap <= 384)
-                    timed_launch(e, 0, k_step_patch<3, kPatchKP, kPatchMinW, false, 2>, dim3(n), dim3(192), e->gain_lds, s, v, env_ids, n, action, prev, noise, flags, status, reward, ar);
-                else
-                    timed_launch(e, 0, k_step_patch<3>, dim3(n), dim3(192), e->gain_lds, s, v, env_ids, n, action, prev, noise, flags, status, reward, ar);
-            else if (e->big_min_items > 0 && n >= e->big_min_items) {
-                View vb = v;  // (six waves per SIMD pay once a launch is many rounds of workgroups: k_step_patch.h)
-                vb.pcap = e->pcap_big;
-                timed_launch(e, 0, k_step_patch<2, IPP_PATCH_BIGKP, 6>, dim3(n), dim3(128), e->lds_big, s, vb, env_ids, n, action, prev, noise, flags, status, reward, ar);
-            } else if (e->patch_waves == 3) {
-                View v2 = v;  // a large launch of a three-wave engine: two waves per item, LDS share of 12 workgroups per CU
-                v2.pcap = e->pcap2;
-                timed_launch(e, 0, k_step_patch<2>, dim3(n), dim3(128), e->lds2, s, v2, env_ids, n, action, prev, noise, flags, status, reward, ar);
-            } else
-                timed_launch(e, 0, k_step_patch<2>, dim3(n), dim3(128), e->gain_lds, s, v, env_ids, n, action, prev, noise, flags, status, reward, ar);
+            // (the budget ledger: the IPP_BUDGET instantiation of the kernel the launch would run otherwise -- budget_launch_error has
+            // refused the split step and the one- / four-wave A/B engines)
+            const PatchVariant& pv = pick(e->pp, n);
+            View vp = v;
+            vp.pcap = pv.pcap;
+            timed_launch(e, pv.split ? 2 : 0, (flags & IPP_BUDGET) ? patch_kernel<true>(pv) : patch_kernel<false>(pv), dim3(n), dim3(64 * pv.waves), pv.lds, s, vp,
+                         env_ids, n, action, prev, noise, flags, status, reward, ar);
+            // split step (k_step_split.h): item-parallel prologue kernel, then one wave per (item, unit)
+            if (pv.split) timed_launch(e, 0, k_step_units<>, dim3(split_grid(n, v.punits)), dim3(64), e->pp.lds_u, s, v, n, flags, reward, ar);
         }
         if (prep_done) (void)hipEventRecord(prep_done, s);
         return;
@@ -601,7 +564,6 @@ int launch_step(Engine* e, const int32_t* env_ids, const int32_t* dst_ids, int n
     HIP_TRY(hipEventRecord(e->ev_begin, s));
     HIP_TRY(hipStreamWaitEvent(e->side, e->ev_begin, 0));
     const int per = ((n + chunks - 1) / chunks + 7) / 8 * 8;
-    int used = 0;
     const bool ordered = e->v.item_order && e->v.item_order_n == n && e->v.mode == IPP_FACTOR && e->v.window_rows > 0 && e->v.T != kWave;  // (k_gain_wave keeps its own item map)
     for (int c = 0, off = 0; off < n; ++c, off += per) {
         const int nc = std::min(per, n - off);
@@ -614,7 +576,6 @@ int launch_step(Engine* e, const int32_t* env_ids, const int32_t* dst_ids, int n
             v.item_order = e->v.item_order + off;
             v.item_order_n = nc;
             launch_chunk<MC, VEC>(e, v, env_ids, dst_ids, nc, action, prev, noise, flags, reward, status, st, e->ev_prep[c], ar);
-            used = c + 1;
             continue;
         }
         v.item_order = nullptr;
@@ -631,9 +592,7 @@ int launch_step(Engine* e, const int32_t* env_ids, const int32_t* dst_ids, int n
         launch_chunk<MC, VEC>(e, v, env_ids ? env_ids + off : nullptr, dst_ids ? dst_ids + off : nullptr, nc,
                               action + 3 * (size_t)off, prev + 3 * (size_t)off, noise ? noise + (size_t)off * MC : nullptr,
                               flags, reward + off, status ? status + off : nullptr, st, e->ev_prep[c], arc);
-        used = c + 1;
     }
-    (void)used;
     HIP_TRY(hipEventRecord(e->ev_end, e->side));
     HIP_TRY(hipStreamWaitEvent(s, e->ev_end, 0));
     HIP_TRY(hipGetLastError());
@@ -803,7 +762,7 @@ int ipp_min_window_rows(const ipp_config* cfg, int32_t* rows) { return ipp_min_w
 int ipp_engine_arena_bytes_prior(const ipp_config* cfg, int32_t kind, uint64_t* bytes) {
     if (!cfg || !bytes) return fail(-1, "null argument");
     Layout L;
-    if (int rc = plan(*cfg, kind, L)) return rc;
+    if (int rc = plan(*cfg, kind, Switches(), L)) return rc;  // (the switches ipp_engine_create_prior will read: the two agree)
     *bytes = L.total;
     return 0;
 }
@@ -814,8 +773,9 @@ int ipp_engine_create(const ipp_config* cfg, int device, void* arena, uint64_t a
 }
 int ipp_engine_create_prior(const ipp_config* cfg, int32_t kind, int device, void* arena, uint64_t arena_bytes, void** engine) {
     if (!cfg || !arena || !engine) return fail(-1, "null argument");
+    const Switches sw;  // (parsed here, once: plan() and everything below see the same values)
     Layout L;
-    if (int rc = plan(*cfg, kind, L)) return rc;
+    if (int rc = plan(*cfg, kind, sw, L)) return rc;
     if (arena_bytes < L.total) return fail(-1, "arena too small: %llu < %llu", (unsigned long long)arena_bytes, (unsigned long long)L.total);
     if ((reinterpret_cast<uintptr_t>(arena) & (kAlign - 1)) != 0) return fail(-1, "arena must be %llu-byte aligned", (unsigned long long)kAlign);
     HIP_TRY(hipSetDevice(device));
@@ -860,13 +820,13 @@ int ipp_engine_create_prior(const ipp_config* cfg, int32_t kind, int device, voi
     e->rect_ok = v.clip_cols && L.MC == 9 && L.VEC == 2 && cfg->x_dim % 2 == 0 && lut_complete;
     e->rect_commit = e->rect_ok && 5 * (2 * cfg->window_rows + 7) <= 2 * cfg->x_dim;
     e->rect_tree = v.clip_cols && L.MC == 9 && cfg->x_dim % L.VEC == 0 && lut_complete && 5 * (2 * cfg->window_rows + 5 + 2 * (L.VEC - 1)) <= 2 * cfg->x_dim;
-    if (const char* rt = getenv("IPP_RECT_TREE")) e->rect_tree = v.clip_cols && L.MC == 9 && cfg->x_dim % L.VEC == 0 && lut_complete && atoi(rt) != 0;  // A/B experiments
-    if (const char* rc = getenv("IPP_RECT")) { e->rect_commit = e->rect_ok && atoi(rc) == 2; e->rect_ok = e->rect_ok && atoi(rc) != 0; }  // A/B: 0 off, 1 predict-only, 2 always
+    if (sw.rect_tree) e->rect_tree = v.clip_cols && L.MC == 9 && cfg->x_dim % L.VEC == 0 && lut_complete && *sw.rect_tree != 0;  // A/B experiments
+    if (sw.rect) { e->rect_commit = e->rect_ok && *sw.rect == 2; e->rect_ok = e->rect_ok && *sw.rect != 0; }  // A/B: 0 off, 1 predict-only, 2 always
     // Rectangle metadata (View::rect_meta, ipp_common.h): steps on rectangle tiles store the new columns on the rectangle
     // only and record it per column; every reader of stored columns masks with it.  Without it the band cells outside the
     // rectangle received zeros from a store-only pass: 75 % of the gain kernel's HBM writes at 100x100, more at 200x200.
     v.rect_meta = (v.clip_cols && L.MC == 9 && cfg->x_dim % L.VEC == 0 && cfg->x_dim <= 256 && cfg->y_dim <= 256 && (e->rect_ok || e->rect_tree)) ? 1 : 0;
-    if (const char* rm = getenv("IPP_RECT_META")) v.rect_meta = v.rect_meta && atoi(rm) != 0;  // A/B experiments
+    if (sw.rect_meta) v.rect_meta = v.rect_meta && *sw.rect_meta != 0;  // A/B experiments
     // Only the rectangle-tile variants of the streaming kernels mask (k_gain_factor.h), so with the metadata on every
     // stream over columns that may carry a true rectangle runs on rectangle tiles: env steps where they exist (VEC = 2;
     // else the env columns are written on band tiles and carry full rectangles), tree steps always.
@@ -875,37 +835,21 @@ int ipp_engine_create_prior(const ipp_config* cfg, int32_t kind, int device, voi
     v.pw = v.ph = v.pstride = v.plw = v.pcap = v.punits = 0;
     v.blk = nullptr; v.blk_stride = 0; v.blk_pos0 = 0;
     e->patch = L.patch;
-    e->patch_waves = L.patch_waves;
     if (L.patch) {
         v.clip_cols = 1;
         v.rect_meta = 1;
         v.pw = L.pg.pw; v.ph = L.pg.ph; v.pstride = L.pg.pstride; v.plw = L.pg.plw; v.punits = L.pg.punits;
-        // column records in LDS: what fits the share of a workgroup when kPatchWavesPerCu waves of the kernel are resident per CU
-        // (the LDS of a workgroup is allocated in granules of 1280 bytes on gfx950: 16 KB would take 13 of the 128)
-        int wgs = kPatchWavesPerCu / L.patch_waves;
-        // (at most 13 granules: 170 records are more than the two register pages of the unit loop hold, and the 8 workgroups of the
-        // default configuration then leave 30 KB of the CU's LDS to the ground-truth kernel that runs beside the steps)
-        const size_t budget = std::min<size_t>((size_t)160 * 1024 / wgs / 1280 * 1280, (size_t)13 * 1280);
-        const size_t fixed = PatchLds::bytes(0, v.plw * v.plw, L.patch_waves, v.punits, cfg->rank_cap);
-        int pcap = fixed + 17 * kPatchRec * 4 <= budget ? (int)((budget - fixed) / (kPatchRec * 4)) - 1 : 16;
-        if (const char* pc = getenv("IPP_PATCH_CAP")) pcap = std::max(8, atoi(pc));  // A/B experiments, overflow tests
-        // (a staging capacity below the rank is a multiple of 8: the m x m algebra sums the records in groups of eight, so S does not
-        // depend on where a record is staged -- solve_wave_fast)
-        v.pcap = pcap >= cfg->rank_cap ? cfg->rank_cap : (pcap & ~7);
         v.blk = reinterpret_cast<float*>(base + L.off_blk);
         v.blk_stride = (int)SplitBlk::floats(v.plw, cfg->rank_cap);
-        {   // split step: LDS of the prologue kernel for kSplitMinWP workgroups per SIMD, of the unit kernel as it comes
-            if (const char* pwv = getenv("IPP_SPLIT_WAVES")) { const int w = atoi(pwv); if (w >= 1 && w <= 3) e->split_waves = w; }  // A/B
-            const size_t budget = (size_t)160 * 1024 / (4 * kSplitMinWP / e->split_waves) / 1280 * 1280;
-            const size_t fixed = PatchLds::bytes(0, 0, 1, v.punits, cfg->rank_cap);
-            int pc = fixed + 8 * kPatchRec * 4 <= budget ? (int)((budget - fixed) / (kPatchRec * 4)) & ~7 : 8;
-            e->pcap_p = pc >= cfg->rank_cap ? cfg->rank_cap : pc;
-            e->lds_p = PatchLds::bytes(e->pcap_p, 0, 1, v.punits, cfg->rank_cap);
-            e->lds_u = SplitLds::bytes(v.plw, cfg->rank_cap);
-            // IPP_SPLIT=<n>: launches of at least n items take the split step (1: all of them, 0: never)
-            e->split_min_items = 0;
-            if (const char* sp = getenv("IPP_SPLIT")) e->split_min_items = std::max(0, atoi(sp));
+        e->pp = make_patch_plan(v, sw);
+        v.pcap = e->pp.tier[0].pcap;
+        // every variant of the plan is an instantiated kernel; where its IPP_BUDGET form is one too, budget steps may run it
+        bool have = patch_kernel<false>(e->pp.split) && tree_patch_kernel(e->pp.tree);
+        for (int i = 0; i < e->pp.n_tiers; ++i) {
+            have = have && patch_kernel<false>(e->pp.tier[i]);
+            e->pp.tier[i].budget = patch_kernel<true>(e->pp.tier[i]) != nullptr;
         }
+        if (!have) { delete e; return fail(-3, "the patch launch plan names a kernel that is not instantiated"); }
     }
     v.win_tiles = L.win_tiles;
     v.cov = reinterpret_cast<float*>(base + L.off_cov);
@@ -950,7 +894,7 @@ int ipp_engine_create_prior(const ipp_config* cfg, int32_t kind, int device, voi
     if (v.mode == IPP_FACTOR && v.window_rows > 0) {
         const size_t MCs = v.meas_cap, LQ = (MCs * MCs + MCs + 3) & ~(size_t)3;
         e->fused = ((v.T == kStepThreads) && v.meas_cap == 9) || e->patch;  // (MC = 25: two launches, see launch_chunk)
-        if (const char* fu = getenv("IPP_FUSED")) e->fused = e->fused && atoi(fu) != 0;  // A/B experiments
+        if (sw.fused) e->fused = e->fused && *sw.fused != 0;  // A/B experiments
         const int waves = v.T / 64;
         // prior table rows: a tile that holds new columns lies within window_rows of the footprint, so
         // |drow| <= window_rows + rows a tile spans + footprint height; farther rows (tall footprints) use sqrt / exp
@@ -969,37 +913,7 @@ int ipp_engine_create_prior(const ipp_config* cfg, int32_t kind, int device, voi
             e->tree_fused_lds = std::max(GainLds<25>::bytes(v.rank_cap, step_work_floats<25>(v.rank_cap), lutf, step_small_floats<25>(), waves, v.win_tiles, v.win_tiles * kWave),
                                          GainLds<25>::bytes(v.rank_cap, step_work_floats<25>(v.rank_cap), lutf, step_small_floats<25>(), waves, v.win_tiles, 0, 0, v.vec));
         }
-        if (e->patch) e->gain_lds = PatchLds::bytes(v.pcap, v.plw * v.plw, e->patch_waves, v.punits, v.rank_cap);
-        if (e->patch && e->patch_waves == 3 && !getenv("IPP_PATCH_CAP")) {
-            // Launch-size rule of the default engine (round 6).  Three waves per item shorten the chains of the heaviest items, which end
-            // a launch of one or two rounds of workgroup slots (2048 items: 55 M env-steps/s against 37 M with two waves); a launch of
-            // many rounds has no tail to shorten and is paid in items in flight: two waves per item are 12 items per CU instead of 8.
-            // Same box, two groups of launches: 8192 envs of 50x50 (4096 items per launch) 64.9 M with three waves against 54.5 M with
-            // two; 16384 envs 62.9 against 66.5 M; 32768 envs (configs[3] share) 61.8-64.3 against 66.1 M; configs[2] 66.1-67.0
-            // against 70.1-71.6 M (profiles/r06_experiments.txt 3).  Same arithmetic per cell, same order: bit-identical results
-            // (tests/test_hip_rect_meta.py).  IPP_PATCH_TWO_MIN=<items> (0: never) for A/B.
-            const size_t budget = (size_t)160 * 1024 / 12 / 1280 * 1280;
-            const size_t fixed = PatchLds::bytes(0, v.plw * v.plw, 2, v.punits, v.rank_cap);
-            int p2 = fixed + 17 * kPatchRec * 4 <= budget ? (int)((budget - fixed) / (kPatchRec * 4)) - 1 : 16;
-            p2 = p2 >= v.rank_cap ? v.rank_cap : (p2 & ~7);  // (below the rank a multiple of 8: solve_wave_fast sums the records in groups of eight)
-            e->pcap2 = std::min(p2, (int)v.pcap);
-            e->lds2 = PatchLds::bytes(e->pcap2, v.plw * v.plw, 2, v.punits, v.rank_cap);
-            e->two_wave_min_items = 6144;
-            if (const char* t = getenv("IPP_PATCH_TWO_MIN")) e->two_wave_min_items = std::max(0, atoi(t));
-        }
-        if (e->patch && (e->patch_waves == 2 || e->two_wave_min_items > 0) && !getenv("IPP_PATCH_CAP")) {
-            // second configuration for large launches: LDS share of 12 workgroups per CU (10 granules of 1280 bytes)
-            const size_t budget = (size_t)160 * 1024 / 12 / 1280 * 1280;
-            const size_t fixed = PatchLds::bytes(0, v.plw * v.plw, 2, v.punits, v.rank_cap);
-            const int pc = fixed + 33 * kPatchRec * 4 <= budget ? (int)((budget - fixed) / (kPatchRec * 4)) - 1 : 0;
-            int min_items = 16384;
-            if (const char* b = getenv("IPP_PATCH_BIG")) min_items = atoi(b);  // A/B: smallest launch that takes it (0: never)
-            if (pc >= 32 && min_items > 0) {
-                e->pcap_big = std::min(pc, (int)(e->patch_waves == 3 ? e->pcap2 : v.pcap));
-                e->lds_big = PatchLds::bytes(e->pcap_big, v.plw * v.plw, 2, v.punits, v.rank_cap);
-                e->big_min_items = min_items;
-            }
-        }
+        if (e->patch) e->gain_lds = e->pp.tier[0].lds;
         if (v.T == kWave && !e->patch)
             e->gain_lds = (LQ + kTileLut) * 4 + (size_t)v.rank_cap * 4 + (8 * MCs) * 4 +
                           (size_t)(v.rank_cap + 8) * 2;
@@ -1021,21 +935,14 @@ int ipp_engine_create_prior(const ipp_config* cfg, int32_t kind, int device, voi
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_prepare<25, IPP_FACTOR>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_prepare<25, IPP_DENSE>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     {  // patch kernels: opt in to more than the default 64 KB of dynamic LDS
-        const int pl = 160 * 1024;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step_patch<1>), hipFuncAttributeMaxDynamicSharedMemorySize, pl);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step_patch<2>), hipFuncAttributeMaxDynamicSharedMemorySize, pl);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step_patch<3>), hipFuncAttributeMaxDynamicSharedMemorySize, pl);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step_patch<3, kPatchKP, kPatchMinW, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, pl);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step_patch<3, kPatchKP, kPatchMinW, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, pl);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step_patch<4>), hipFuncAttributeMaxDynamicSharedMemorySize, pl);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step_patch<2, IPP_PATCH_BIGKP, 6>), hipFuncAttributeMaxDynamicSharedMemorySize, pl);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step_patch<1, kPatchKP, kSplitMinWP, true>), hipFuncAttributeMaxDynamicSharedMemorySize, pl);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step_patch<2, kPatchKP, kSplitMinWP, true>), hipFuncAttributeMaxDynamicSharedMemorySize, pl);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step_patch<3, kPatchKP, kSplitMinWP, true>), hipFuncAttributeMaxDynamicSharedMemorySize, pl);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tree_patch<2>), hipFuncAttributeMaxDynamicSharedMemorySize, pl);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tree_patch<3>), hipFuncAttributeMaxDynamicSharedMemorySize, pl);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tree_patch<3, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, pl);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tree_patch<4>), hipFuncAttributeMaxDynamicSharedMemorySize, pl);
+        auto opt_in = [](auto* kernel) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); };
+        // (the plain form and the IPP_BUDGET form; where there is none, BUD = HASBUD = false names the plain form again)
+#define X(NW, KPN, MINW, SPLIT, RJN, HASBUD) opt_in(k_step_patch<NW, KPN, MINW, SPLIT, RJN, false>); opt_in(k_step_patch<NW, KPN, MINW, SPLIT, RJN, HASBUD>);
+        IPP_STEP_PATCH_KERNELS(X)
+#undef X
+#define X(NW, RJN) opt_in(k_tree_patch<NW, RJN>);
+        IPP_TREE_PATCH_KERNELS(X)
+#undef X
     }
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_grf_conv<5, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_grf_conv<8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024);
@@ -1059,7 +966,7 @@ int ipp_engine_create_prior(const ipp_config* cfg, int32_t kind, int device, voi
         // and the scratch round trip of L^-1 | Q cost more than the occupancy gains); IPP_TREE_SPLIT=<min items> / 0
         e->tree_gain_lds = (GainLds<9>::bytes(v.rank_cap, 0, e->lut_rows * v.W, 0, e->tree_T / kWave, v.win_tiles, 0, v.rank_cap, v.vec) + 15) & ~(size_t)15;
         e->tree_split_min = 2048;
-        if (const char* ts = getenv("IPP_TREE_SPLIT")) e->tree_split_min = atoi(ts);
+        if (sw.tree_split) e->tree_split_min = *sw.tree_split;
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tree_prepare<9>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tree_gain<9, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->tree_gain_lds);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tree_gain<9, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->tree_gain_lds);
@@ -1104,7 +1011,7 @@ int ipp_engine_create_prior(const ipp_config* cfg, int32_t kind, int device, voi
                 if (n == 50) (void)hipFuncSetAttribute((const void*)&k_grf_hartley<4, 4, 13>, hipFuncAttributeMaxDynamicSharedMemorySize, hl);
                 if (n == 100) (void)hipFuncSetAttribute((const void*)&k_grf_hartley<7, 8, 25>, hipFuncAttributeMaxDynamicSharedMemorySize, hl);
                 e->grf_fft = (n == 50 || n == 100);
-                if (const char* gf = getenv("IPP_GRF_FFT")) e->grf_fft = e->grf_fft && atoi(gf) != 0;  // A/B: the GEMM form
+                if (sw.grf_fft) e->grf_fft = e->grf_fft && *sw.grf_fft != 0;  // A/B: the GEMM form
             }
         }
         if (e->grf_dft) {
@@ -1117,7 +1024,7 @@ int ipp_engine_create_prior(const ipp_config* cfg, int32_t kind, int device, voi
             e->grf_kc = (int)std::max(1L, std::min((long)(n / 2 + 1), (budget - fixed) / ((long)n * 40)));
         }
     }
-    if (const char* ch = getenv("IPP_STEP_CHUNKS")) e->step_chunks = atoi(ch);
+    if (sw.step_chunks) e->step_chunks = *sw.step_chunks;
     if (hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking) == hipSuccess) {
         (void)hipEventCreateWithFlags(&e->ev_begin, hipEventDisableTiming);
         (void)hipEventCreateWithFlags(&e->ev_end, hipEventDisableTiming);
@@ -1174,10 +1081,10 @@ int ipp_engine_info(void* engine, ipp_info* out) {
     out->step_lds_bytes = e->gain_lds;
     out->fused_step = e->fused ? 1 : 0;
     out->patch_layout = e->patch ? 1 : 0;
-    out->patch_waves = e->patch ? e->patch_waves : 0;
-    out->patch_big_min_items = e->patch ? e->big_min_items : 0;
-    out->patch_two_wave_min_items = e->patch ? e->two_wave_min_items : 0;
-    out->patch_split_min_items = e->patch ? e->split_min_items : 0;
+    out->patch_waves = e->patch ? e->pp.tier[0].waves : 0;
+    out->patch_big_min_items = e->patch ? e->pp.tier[e->pp.big_tier].min_items : 0;  // (tier[0].min_items = 0: no such tier)
+    out->patch_two_wave_min_items = e->patch ? e->pp.tier[e->pp.two_wave_tier].min_items : 0;
+    out->patch_split_min_items = e->patch ? e->pp.split.min_items : 0;
     return 0;
 }
 
@@ -1269,8 +1176,8 @@ static const char* budget_launch_error(const Engine* e, uint32_t flags, int n, c
     if (flags & IPP_PREDICT_ONLY) return "IPP_BUDGET: not with IPP_PREDICT_ONLY (the ledger charges committed steps)";
     if (env_ids) return "IPP_BUDGET: full-batch in-place steps only (env_ids == NULL)";
     if (n > e->v.cap) return "IPP_BUDGET: more items than env slots";
-    if (e->split_min_items > 0 && n >= e->split_min_items) return "IPP_BUDGET: not on the split step (IPP_SPLIT)";
-    if (e->patch_waves != 2 && e->patch_waves != 3) return "IPP_BUDGET: engines of two or three waves per item only (IPP_PATCH_WAVES)";
+    if (pick(e->pp, n).split) return "IPP_BUDGET: not on the split step (IPP_SPLIT)";
+    if (!pick(e->pp, n).budget) return "IPP_BUDGET: engines of two or three waves per item only (IPP_PATCH_WAVES)";
     if (e->step_chunks > 1) return "IPP_BUDGET: not with a chunked step (IPP_STEP_CHUNKS)";
     if (flags & IPP_RESET_ON_DONE) {
         if (reset_src || reset_gt) return "IPP_RESET_ON_DONE: the resets come from the ledger (reset_src and reset_gt must be NULL)";
@@ -1595,18 +1502,10 @@ static int tree_step_impl(void* engine, const int32_t* root_ids, const int32_t* 
     e->last_n = n;
     const View& v = e->v;
     if (e->patch) {  // tree nodes as patches: one fused kernel for every launch size (k_tree_patch.h)
-        // (LDS sized for the waves this kernel really has: the step kernel may run 1 wave per item -- IPP_PATCH_WAVES --, the tree kernel 2 to 4)
-        const int nw = e->patch_waves >= 2 ? e->patch_waves : 2;
-        const size_t tlds = PatchLds::bytes(v.pcap, v.plw * v.plw, nw, v.punits, v.rank_cap);
+        const PatchVariant& pv = e->pp.tree;
         const TreeEdgeOut eo = edge_out ? *edge_out : TreeEdgeOut{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
-        if (nw == 3 && v.rank_cap <= 192)
-            timed_launch(e, 0, k_tree_patch<3, 1>, dim3(n), dim3(192), tlds, s, v, e->tv, root_ids, path_ids, new_ids, n, action, prev_action, flags, status, reward, n_dev, eo);
-        else if (nw == 3)
-            timed_launch(e, 0, k_tree_patch<3>, dim3(n), dim3(192), tlds, s, v, e->tv, root_ids, path_ids, new_ids, n, action, prev_action, flags, status, reward, n_dev, eo);
-        else if (nw == 4)
-            timed_launch(e, 0, k_tree_patch<4>, dim3(n), dim3(256), tlds, s, v, e->tv, root_ids, path_ids, new_ids, n, action, prev_action, flags, status, reward, n_dev, eo);
-        else
-            timed_launch(e, 0, k_tree_patch<2>, dim3(n), dim3(128), tlds, s, v, e->tv, root_ids, path_ids, new_ids, n, action, prev_action, flags, status, reward, n_dev, eo);
+        timed_launch(e, 0, tree_patch_kernel(pv), dim3(n), dim3(64 * pv.waves), pv.lds, s, v, e->tv, root_ids, path_ids, new_ids, n, action, prev_action, flags, status,
+                     reward, n_dev, eo);
         HIP_TRY(hipGetLastError());
         return 0;
     }

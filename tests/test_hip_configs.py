@@ -55,11 +55,11 @@ def test_fullsize_batch_invariants_subset_parity_and_reproducibility(grid, B, T,
     full = IPPEngine(cfg, capacity=B, state="factor", rank_cap=9 * T, window_rows=-1, fixed_prior=True)
     exact = IPPEngine(cfg, capacity=S, state="factor", rank_cap=9 * T, window_rows=0)
     # the bench's path: window from the fixed prior, factor columns as compact patches, k_step_patch -- and for launches of this size
-    # its six-waves-per-SIMD instantiation (csrc/ipp_engine.hip patch_layout() / launch_chunk()); a regression in the selection rules
+    # its six-waves-per-SIMD instantiation (csrc/ipp_engine.hip patch_layout(), csrc/patch_launch.h pick()); a regression in the selection rules
     # would put these configs back on the band-tile kernels with every numeric check below still green
     assert full.info.window_rows == 10
     assert full.info.patch_layout == 1 and full.info.fused_step == 1 and full.info.patch_waves == 3
-    # launches of this size (32768 items, or 16384 per group) run two waves per item, in the four-rows-per-group form (launch_chunk)
+    # launches of this size (32768 items, or 16384 per group) run two waves per item, in the four-rows-per-group form (the tiers of csrc/patch_launch.h)
     assert full.info.patch_two_wave_min_items == 6144 and full.info.patch_big_min_items == 16384
     # ... and an arena of this size comes from the virtual-memory API in 1-GiB chunks at a 1-GiB-aligned address (a silent fall-back to the
     # allocator's memory would cost 15-20 % of the step rate with every numeric check below still green); the small exact engine stays on torch

@@ -1,4 +1,4 @@
-"""The launch-size rule of the patch step kernel (csrc/ipp_engine.hip launch_chunk, ipp_info.patch_two_wave_min_items): large launches
+"""The launch-size rule of the patch step kernel (csrc/patch_launch.h make_patch_plan / pick, ipp_info.patch_two_wave_min_items): large launches
 run two waves per item (k_step_patch<2>, from 16384 items k_step_patch<2, 4, 6>), small ones three (k_step_patch<3>).  Same arithmetic
 per cell in the same order (mapping/mappings.py:178-197; planning/common/rewards.py:8-31), so which instantiation a launch took must
 not show in a single bit -- rewards, planes, ranks, ground truths -- through scheduled resets, on one launch per step and on two groups."""

@@ -830,6 +830,49 @@ int ipp_replay_gather(const ipp_selfplay* sp, int32_t n, int32_t copies, int32_t
                       const int32_t* committed_cum, uint64_t seed, uint64_t subsequence, float* states, float* policy, uint8_t* mask,
                       double* value, double* reward, int64_t* index, int32_t* offsets, void* stream);
 
+/*
+ * Prioritised replay over the same ring (csrc/k_replay_per.h): PrioritizedExperienceReplayBuffer, replay_buffers.py:104-141, with the
+ * priorities, their prefix sums, the draws and the weights in device memory.  These calls read only num_envs, slots, device and r_flags
+ * of `sp` (ipp_replay_gather_rows: the whole ring), priority [dev] double [S B].  fp64 in a fixed order: no floating-point atomics, the
+ * same inputs give the same bits in every run.
+ */
+#define IPP_REPLAY_SCAN_TILE 2048 /* ring rows per workgroup of the prefix sum: ipp_replay_mass needs ceil(S B / tile) doubles of scratch */
+
+/*
+ * `self.priorities = np.ones(L) / L` (:119) over the rows committed now: count [dev] uint64 [1] <- their number L, priority[r] <- 1 / L
+ * on them and 0 on every other row (rows committed later are never drawn: the reference's file list is fixed at construction too).
+ */
+int ipp_replay_priority_reset(const ipp_selfplay* sp, double* priority, uint64_t* count, void* stream);
+/*
+ * `probabilities = self.priorities ** self.alpha` (:126), unnormalised, and its running sum: mass[r] = priority[r]^alpha where row r is
+ * committed (r_flags == 2) and its priority is finite and > 0, else 0; cum [dev] double [S B] <- the inclusive prefix sums of the mass
+ * over all ring rows (a multi-workgroup scan, error <= rows x 2^-52 x total).  scratch [dev]: scratch_doubles >= ceil(S B /
+ * IPP_REPLAY_SCAN_TILE) doubles.
+ */
+int ipp_replay_mass(const ipp_selfplay* sp, const double* priority, double alpha, double* cum, double* scratch, uint64_t scratch_doubles,
+                    void* stream);
+/*
+ * `np.random.choice(L, size=n, p=probabilities)` and the importance-sampling weights (:129, :135-136) from ipp_replay_mass's `cum` of the
+ * same priorities and alpha: with T = the total mass and u_i the uniform at counter i of `subsequence` (ipp_replay_gather's), index[i] =
+ * the first row whose prefix mass exceeds u_i T (cdf.searchsorted(u, side="right"); the last row with mass if rounding leaves none);
+ * weight[i] = (P_i L)^-beta over the largest of the n, as float, with P_i = mass[index[i]] / T from the row's own mass and L =
+ * committed_count.  T == 0: index -1, weight NaN.  index [dev] int64 [n], weight [dev] float [n].
+ */
+int ipp_replay_draw_per(const ipp_selfplay* sp, const double* priority, const double* cum, double alpha, double beta,
+                        int64_t committed_count, int32_t n, uint64_t seed, uint64_t subsequence, int64_t* index, float* weight, void* stream);
+/*
+ * ipp_replay_gather's rows for given ring rows (`load_batch_from_disk(sample_file_paths)`, :131-133; no augmented copies, :114): output
+ * row o is ring row rows[o] ([dev] int64 [n]; outside the ring, such as -1: NaN planes, value and reward, zero policy and mask).
+ */
+int ipp_replay_gather_rows(const ipp_selfplay* sp, int32_t n, int32_t channels, int32_t side, const float* planes, const int64_t* rows,
+                           float* states, float* policy, uint8_t* mask, double* value, double* reward, void* stream);
+/*
+ * `self.priorities[indices] = priorities` (:140-141): priority[index[i]] = value[i]; where an index repeats, its last occurrence wins
+ * (NumPy's assignment); an index outside the ring (-1: an empty draw) is skipped.  index [dev] int64 [n], value [dev] double [n].
+ */
+int ipp_replay_priority_update(const ipp_selfplay* sp, double* priority, const int64_t* index, const double* value, int32_t n,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

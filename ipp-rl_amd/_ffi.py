@@ -18,11 +18,12 @@ IPP_BUDGET_STREAM = 3 << 40
 # Philox subsequence bases of the self-play draws (ipp_selfplay_record / _commit, ipp_replay_gather)
 IPP_SP_ACTION_STREAM, IPP_SP_INIT_STREAM, IPP_SP_TIE_STREAM, IPP_SP_ARGMAX_STREAM, IPP_REPLAY_STREAM = (4 << 40, 5 << 40, 6 << 40, 7 << 40,
                                                                                                        8 << 40)
+IPP_REPLAY_SCAN_TILE = 2048  # ring rows per workgroup of ipp_replay_mass's prefix sum (its scratch: one double per tile)
 IPP_FIELD_GRF, IPP_FIELD_HOTSPOT, IPP_FIELD_SPLIT = 0, 1, 2
 STATUS_OK, STATUS_CHOL_FALLBACK, STATUS_NOT_PD, STATUS_RANK_FULL, STATUS_BAD_FOOTPRINT = 0, 1, 2, 3, 4
 IPP_MAX_MEAS = 25
 ABI_VERSION = 17
-AB_MIN_ABI = 13  # oldest library tools/ab_kernels.py may load under IPP_AB_OLD_LIB (v14 added the ipp_arena_* calls, v15 the budget ledger calls, v16 the *_prior calls, v17 the field calls; ipp_feature_planes and ipp_mcts_plane_entries were added later WITHOUT a bump -- tests pin 17 -- so an older v17 library lacks them and the A/B loader leaves them unbound; nothing else)
+AB_MIN_ABI = 13  # oldest library tools/ab_kernels.py may load under IPP_AB_OLD_LIB (v14 added the ipp_arena_* calls, v15 the budget ledger calls, v16 the *_prior calls, v17 the field calls; ipp_feature_planes, ipp_mcts_plane_entries and the prioritised-replay calls (ipp_replay_priority_reset .. _update) were added later WITHOUT a bump -- tests pin 17 -- so an older v17 library lacks them and the A/B loader leaves them unbound; nothing else)
 IPP_ARENA_HIPMALLOC, IPP_ARENA_VMM = 0, 1
 
 
@@ -193,6 +194,12 @@ PROTOTYPES = {
     "ipp_selfplay_commit": (C.c_int, [C.POINTER(IppSelfPlay), C.c_int64, _P]),
     "ipp_replay_gather": (C.c_int, [C.POINTER(IppSelfPlay), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_uint64, C.c_uint64,
                                     _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ipp_replay_priority_reset": (C.c_int, [C.POINTER(IppSelfPlay), _P, _P, _P]),
+    "ipp_replay_mass": (C.c_int, [C.POINTER(IppSelfPlay), _P, C.c_double, _P, _P, C.c_uint64, _P]),
+    "ipp_replay_draw_per": (C.c_int, [C.POINTER(IppSelfPlay), _P, _P, C.c_double, C.c_double, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64,
+                                      _P, _P, _P]),
+    "ipp_replay_gather_rows": (C.c_int, [C.POINTER(IppSelfPlay), C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ipp_replay_priority_update": (C.c_int, [C.POINTER(IppSelfPlay), _P, _P, _P, C.c_int32, _P]),
 }
 
 _lib = None

@@ -33,6 +33,7 @@
 #include "k_tree_patch.h"
 #include "k_mcts.h"
 #include "k_selfplay.h"
+#include "k_replay_per.h"
 #include "k_prepare.h"
 #include "patch_launch.h"
 
@@ -1785,6 +1786,99 @@ int ipp_replay_gather(const ipp_selfplay* sp, int32_t n, int32_t copies, int32_t
     HIP_TRY(hipSetDevice(sp->device));
     const size_t lds = (size_t)sp->kmax * (sizeof(float) + sizeof(int32_t));
     hipLaunchKernelGGL(k_sp_gather, dim3((unsigned)blocks), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), *sp, g);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+namespace {
+// the prioritised sampler's calls read the ring's size and flags only
+int replay_ring_check(const ipp_selfplay* sp) {
+    if (!sp) return fail(-1, "null argument");
+    if (sp->num_envs <= 0 || sp->slots <= 0 || (long long)sp->num_envs * sp->slots > INT32_MAX)
+        return fail(-1, "num_envs = %d, slots = %d: need both > 0 and a ring of < 2^31 rows", sp->num_envs, sp->slots);
+    if (!sp->r_flags) return fail(-1, "ipp_selfplay: null r_flags");
+    return 0;
+}
+}  // namespace
+
+int ipp_replay_priority_reset(const ipp_selfplay* sp, double* priority, uint64_t* count, void* stream) {
+    if (int rc = replay_ring_check(sp)) return rc;
+    if (!priority || !count) return fail(-1, "null argument");
+    const long long cap = (long long)sp->num_envs * sp->slots;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(sp->device));
+    HIP_TRY(hipMemsetAsync(count, 0, sizeof(uint64_t), s));
+    const unsigned blocks = (unsigned)((cap + kPerThreads - 1) / kPerThreads);
+    hipLaunchKernelGGL(k_per_count, dim3(blocks), dim3(kPerThreads), 0, s, sp->r_flags, cap, reinterpret_cast<unsigned long long*>(count));
+    hipLaunchKernelGGL(k_per_reset, dim3(blocks), dim3(kPerThreads), 0, s, sp->r_flags, cap,
+                       reinterpret_cast<const unsigned long long*>(count), priority);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ipp_replay_mass(const ipp_selfplay* sp, const double* priority, double alpha, double* cum, double* scratch, uint64_t scratch_doubles,
+                    void* stream) {
+    if (int rc = replay_ring_check(sp)) return rc;
+    if (!priority || !cum || !scratch) return fail(-1, "null argument");
+    if (!(alpha >= 0.0) || !(alpha < INFINITY)) return fail(-1, "alpha = %g outside [0, inf)", alpha);
+    const long long cap = (long long)sp->num_envs * sp->slots;
+    const long long tiles = (cap + IPP_REPLAY_SCAN_TILE - 1) / IPP_REPLAY_SCAN_TILE;
+    if (scratch_doubles < (uint64_t)tiles)
+        return fail(-1, "scratch of %llu doubles, ipp_replay_mass needs %lld for %lld rows", (unsigned long long)scratch_doubles, tiles, cap);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(sp->device));
+    hipLaunchKernelGGL(k_per_mass_tile, dim3((unsigned)tiles), dim3(kPerThreads), 0, s, sp->r_flags, priority, cap, alpha, cum, scratch);
+    hipLaunchKernelGGL(k_per_scan_tiles, dim3(1), dim3(kPerThreads), 0, s, scratch, tiles);
+    hipLaunchKernelGGL(k_per_scan_rows, dim3((unsigned)tiles), dim3(kPerThreads), 0, s, cap, scratch, cum);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ipp_replay_draw_per(const ipp_selfplay* sp, const double* priority, const double* cum, double alpha, double beta,
+                        int64_t committed_count, int32_t n, uint64_t seed, uint64_t subsequence, int64_t* index, float* weight, void* stream) {
+    if (int rc = replay_ring_check(sp)) return rc;
+    if (!priority || !cum || !index || !weight) return fail(-1, "null argument");
+    if (n < 1 || committed_count < 1) return fail(-1, "n = %d, committed_count = %lld: need both >= 1", n, (long long)committed_count);
+    if (!(alpha >= 0.0) || !(alpha < INFINITY) || !(beta >= 0.0) || !(beta < INFINITY))
+        return fail(-1, "alpha = %g, beta = %g outside [0, inf)", alpha, beta);
+    PerDraw d{};
+    d.n = n; d.cap = (long long)sp->num_envs * sp->slots; d.priority = priority; d.cum = cum;
+    d.alpha = alpha; d.beta = beta; d.L = (double)committed_count; d.seed = seed; d.subseq = subsequence;
+    d.index = index; d.weight = weight;
+    HIP_TRY(hipSetDevice(sp->device));
+    hipLaunchKernelGGL(k_per_draw, dim3(1), dim3(kPerThreads), 0, reinterpret_cast<hipStream_t>(stream), *sp, d);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ipp_replay_gather_rows(const ipp_selfplay* sp, int32_t n, int32_t channels, int32_t side, const float* planes, const int64_t* rows,
+                           float* states, float* policy, uint8_t* mask, double* value, double* reward, void* stream) {
+    if (int rc = selfplay_check(sp)) return rc;
+    if (n < 1 || channels < 0) return fail(-1, "n = %d, channels = %d", n, channels);
+    if (channels > 0 && (side < 1 || !planes || !states)) return fail(-1, "planes need side >= 1 and the planes / states buffers");
+    if (!rows || !policy || !mask || !value || !reward) return fail(-1, "null argument");
+    const long long blocks = (long long)n * (channels + 1);
+    if (blocks > INT32_MAX) return fail(-1, "%lld blocks: minibatch too large", blocks);
+    SpGather g{};
+    g.n = n; g.copies = 1; g.C = channels; g.side = side; g.A = sp->num_actions; g.kmax = sp->kmax;
+    g.cap = (long long)sp->num_envs * sp->slots;
+    g.planes = planes; g.states = states; g.policy = policy; g.mask = mask; g.value = value; g.reward = reward;
+    HIP_TRY(hipSetDevice(sp->device));
+    const size_t lds = (size_t)sp->kmax * (sizeof(float) + sizeof(int32_t));
+    hipLaunchKernelGGL(k_sp_gather_rows, dim3((unsigned)blocks), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), *sp, g, rows);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ipp_replay_priority_update(const ipp_selfplay* sp, double* priority, const int64_t* index, const double* value, int32_t n,
+                               void* stream) {
+    if (int rc = replay_ring_check(sp)) return rc;
+    if (n < 0) return fail(-1, "n = %d < 0", n);
+    if (n == 0) return 0;
+    if (!priority || !index || !value) return fail(-1, "null argument");
+    HIP_TRY(hipSetDevice(sp->device));
+    hipLaunchKernelGGL(k_per_update, dim3((unsigned)((n + kPerThreads - 1) / kPerThreads)), dim3(kPerThreads), 0,
+                       reinterpret_cast<hipStream_t>(stream), (long long)sp->num_envs * sp->slots, (int)n, index, value, priority);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -1,5 +1,5 @@
 // Batched self-play on the device (planning/mcts_zero/episode_generators.py:102-184 for every env at once) and the replay
-// buffer's minibatch (planning/mcts_zero/replay_buffers.py:58-101).  Three kernels:
+// buffer's minibatch (planning/mcts_zero/replay_buffers.py:58-101).  The kernels:
 //   k_sp_record   one wave per env: the read-out's post-processing (one-hot arg-max for temperature 0, mcts.py:134-138), the
 //                 inverse-CDF draw of np.random.choice(len(policy), p=policy) (:135), the waypoint, the sparse policy / valid set into
 //                 the env's ring row, and the episode end of a root without a policy (`policy is None: break`, :130-131)
@@ -7,7 +7,8 @@
 //                 all its rows in fp64 (:158-164), the committed flags, the episode's value, the next episode's first waypoint
 //                 (sample_init_action, :51, :60-62) and the next step's tie-break uniform
 //   k_sp_gather   store-bound: minibatch rows drawn uniformly from the committed ones, planes shifted by ReplicationPad2d(4) +
-//                 RandomCrop (one offset per augmented copy), policies and masks densified to [A]
+//                 RandomCrop (one offset per augmented copy), policies and masks densified to [A]; k_sp_gather_rows: the same rows
+//                 for a given index array (the prioritised sampler, k_replay_per.h)
 // Every draw is a Philox4x32-10 uniform keyed on the GLOBAL env id (include/ipp_engine.h, IPP_SP_*_STREAM), so shards agree.
 #pragma once
 #include "ipp_common.h"
@@ -209,64 +210,57 @@ struct SpGather {
     float* states; float* policy; uint8_t* mask; double* value; double* reward; int64_t* index; int32_t* offsets;
 };
 
-// block b: output row o = b / (C + 1) (draw o % n of copy o / n), channel b % (C + 1); channel C = the row's policy, mask, value,
-// reward and index
-__global__ __launch_bounds__(256) void k_sp_gather(ipp_selfplay sp, SpGather g) {
-    extern __shared__ double sp_lds[];
-    __shared__ int s_k;
-    const long long b = blockIdx.x;
-    const int o = (int)(b / (g.C + 1)), ch = (int)(b % (g.C + 1));
-    const int copy = o / g.n, i = o % g.n;
-    const long long row = sp_draw_row(g.cum, g.cap, i, g.subseq, g.seed);
-    const int oi = sp_offset(copy, 0, g.subseq, g.seed), oj = sp_offset(copy, 1, g.subseq, g.seed);
-    if (ch < g.C) {
-        const int N = g.side, dy = oi - 4, dx = oj - 4;
-        const size_t NN = (size_t)N * N;
-        float* dst = g.states + ((size_t)o * g.C + ch) * NN;
-        if (row < 0) {
-            for (size_t q = threadIdx.x; q < NN; q += blockDim.x) dst[q] = __int_as_float(0x7fc00000);
-            return;
-        }
-        const float* src = g.planes + ((size_t)row * g.C + ch) * NN;
-        // out[y][x] = in[clamp(y + i - 4)][clamp(x + j - 4)]: ReplicationPad2d(4), then the crop at (i, j)
-        if ((N & 3) == 0) {  // (rows of a multiple of 4 floats: 16-byte stores, 16-byte loads where the row is not shifted)
-            for (size_t q = 4 * (size_t)threadIdx.x; q < NN; q += 4 * (size_t)blockDim.x) {
-                const int y = (int)(q / N), x = (int)(q % N);
-                const int sy = min(max(y + dy, 0), N - 1);
-                const float* srow = src + (size_t)sy * N;
-                float4 v;
-                if (dx == 0) {
-                    v = *reinterpret_cast<const float4*>(srow + x);
-                } else {
-                    v.x = srow[min(max(x + dx, 0), N - 1)];
-                    v.y = srow[min(max(x + 1 + dx, 0), N - 1)];
-                    v.z = srow[min(max(x + 2 + dx, 0), N - 1)];
-                    v.w = srow[min(max(x + 3 + dx, 0), N - 1)];
-                }
-                *reinterpret_cast<float4*>(dst + q) = v;
-            }
-        } else {
-            for (size_t q = threadIdx.x; q < NN; q += blockDim.x) {
-                const int y = (int)(q / N), x = (int)(q % N);
-                dst[q] = src[(size_t)min(max(y + dy, 0), N - 1) * N + min(max(x + dx, 0), N - 1)];
-            }
-        }
+// channel ch of output row o: ring row `row` shifted by the offset (oi, oj) (NaN when row < 0)
+__device__ __forceinline__ void sp_gather_plane(const SpGather& g, long long row, int o, int ch, int oi, int oj) {
+    const int N = g.side, dy = oi - 4, dx = oj - 4;
+    const size_t NN = (size_t)N * N;
+    float* dst = g.states + ((size_t)o * g.C + ch) * NN;
+    if (row < 0) {
+        for (size_t q = threadIdx.x; q < NN; q += blockDim.x) dst[q] = __int_as_float(0x7fc00000);
         return;
     }
-    // dense policy and mask over the A actions from the row's ascending valid set (-1 padding at the end)
+    const float* src = g.planes + ((size_t)row * g.C + ch) * NN;
+    // out[y][x] = in[clamp(y + i - 4)][clamp(x + j - 4)]: ReplicationPad2d(4), then the crop at (i, j)
+    if ((N & 3) == 0) {  // (rows of a multiple of 4 floats: 16-byte stores, 16-byte loads where the row is not shifted)
+        for (size_t q = 4 * (size_t)threadIdx.x; q < NN; q += 4 * (size_t)blockDim.x) {
+            const int y = (int)(q / N), x = (int)(q % N);
+            const int sy = min(max(y + dy, 0), N - 1);
+            const float* srow = src + (size_t)sy * N;
+            float4 v;
+            if (dx == 0) {
+                v = *reinterpret_cast<const float4*>(srow + x);
+            } else {
+                v.x = srow[min(max(x + dx, 0), N - 1)];
+                v.y = srow[min(max(x + 1 + dx, 0), N - 1)];
+                v.z = srow[min(max(x + 2 + dx, 0), N - 1)];
+                v.w = srow[min(max(x + 3 + dx, 0), N - 1)];
+            }
+            *reinterpret_cast<float4*>(dst + q) = v;
+        }
+    } else {
+        for (size_t q = threadIdx.x; q < NN; q += blockDim.x) {
+            const int y = (int)(q / N), x = (int)(q % N);
+            dst[q] = src[(size_t)min(max(y + dy, 0), N - 1) * N + min(max(x + dx, 0), N - 1)];
+        }
+    }
+}
+
+// output row o from ring row `row`: dense policy and mask over the A actions from the row's ascending valid set (-1 padding at the end),
+// value and reward (zeros / NaN when row < 0).  lds: kmax floats + kmax int32, s_k: one int of LDS
+__device__ __forceinline__ void sp_gather_sample(const ipp_selfplay& sp, const SpGather& g, long long row, int o, double* lds, int* s_k) {
     const int kmax = g.kmax;
-    float* s_p = reinterpret_cast<float*>(sp_lds);
-    int32_t* s_i = reinterpret_cast<int32_t*>(sp_lds) + kmax;
-    if (threadIdx.x == 0) s_k = 0;
+    float* s_p = reinterpret_cast<float*>(lds);
+    int32_t* s_i = reinterpret_cast<int32_t*>(lds) + kmax;
+    if (threadIdx.x == 0) *s_k = 0;
     __syncthreads();
     for (int k = threadIdx.x; k < kmax; k += blockDim.x) {
         const int32_t a = row >= 0 ? sp.r_idx[(size_t)row * kmax + k] : -1;
         s_i[k] = a;
         s_p[k] = row >= 0 ? sp.r_policy[(size_t)row * kmax + k] : 0.0f;
-        if (a >= 0) atomicMax(&s_k, k + 1);
+        if (a >= 0) atomicMax(s_k, k + 1);
     }
     __syncthreads();
-    const int K = s_k;
+    const int K = *s_k;
     float* pol = g.policy + (size_t)o * g.A;
     uint8_t* msk = g.mask + (size_t)o * g.A;
     for (int a = threadIdx.x; a < g.A; a += blockDim.x) {
@@ -283,9 +277,41 @@ __global__ __launch_bounds__(256) void k_sp_gather(ipp_selfplay sp, SpGather g) 
         const double nan = __longlong_as_double(0x7ff8000000000000ll);
         g.value[o] = row >= 0 ? sp.r_value[row] : nan;
         g.reward[o] = row >= 0 ? sp.r_reward[row] : nan;
+    }
+}
+
+// block b: output row o = b / (C + 1) (draw o % n of copy o / n), channel b % (C + 1); channel C = the row's policy, mask, value,
+// reward and index
+__global__ __launch_bounds__(256) void k_sp_gather(ipp_selfplay sp, SpGather g) {
+    extern __shared__ double sp_lds[];
+    __shared__ int s_k;
+    const long long b = blockIdx.x;
+    const int o = (int)(b / (g.C + 1)), ch = (int)(b % (g.C + 1));
+    const int copy = o / g.n, i = o % g.n;
+    const long long row = sp_draw_row(g.cum, g.cap, i, g.subseq, g.seed);
+    const int oi = sp_offset(copy, 0, g.subseq, g.seed), oj = sp_offset(copy, 1, g.subseq, g.seed);
+    if (ch < g.C) {
+        sp_gather_plane(g, row, o, ch, oi, oj);
+        return;
+    }
+    sp_gather_sample(sp, g, row, o, sp_lds, &s_k);
+    if (threadIdx.x == 0) {
         g.index[o] = row;
         if (i == 0) { g.offsets[2 * copy] = oi; g.offsets[2 * copy + 1] = oj; }
     }
+}
+
+// The same minibatch for given ring rows (rows[o]; outside [0, cap): an empty row, NaN), unshifted: the prioritised sampler's gather
+// (k_replay_per.h draws the rows).  block b: output row b / (C + 1), channel b % (C + 1) as above
+__global__ __launch_bounds__(256) void k_sp_gather_rows(ipp_selfplay sp, SpGather g, const int64_t* __restrict__ rows) {
+    extern __shared__ double sp_lds[];
+    __shared__ int s_k;
+    const long long b = blockIdx.x;
+    const int o = (int)(b / (g.C + 1)), ch = (int)(b % (g.C + 1));
+    long long row = rows[o];
+    if (row < 0 || row >= g.cap) row = -1;
+    if (ch < g.C) sp_gather_plane(g, row, o, ch, 4, 4);
+    else sp_gather_sample(sp, g, row, o, sp_lds, &s_k);
 }
 
 }  // namespace ipp

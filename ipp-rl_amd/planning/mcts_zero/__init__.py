@@ -1,1 +1,1 @@
-from .selfplay import ReplayBuffer, SelfPlay  # noqa: F401
+from .selfplay import PrioritizedReplay, ReplayBuffer, SelfPlay  # noqa: F401

@@ -21,11 +21,14 @@ Nothing in the loop reads the device from the host beyond the search's one count
 Draws (include/ipp_engine.h, IPP_SP_*_STREAM): the loop's own draws are Philox4x32-10 uniforms keyed on (seed, global env id, episode,
 depth); the search's draws (Dirichlet noise, random tie breaks: k_mcts.h hashes) are keyed on env_id_offset + root; so N shards with
 contiguous env_id_offset produce the samples of one process.  Minibatch draws are keyed on the buffer's draw count and the draw index.  Ring: S step slots of B rows, the sample of env e at step t in row
-(t mod S) B + e; S > max_episode_steps keeps every row of a running episode.  Replay minibatches: ReplayBuffer.sample.
+(t mod S) B + e; S > max_episode_steps keeps every row of a running episode.  Replay minibatches: ReplayBuffer.sample (uniform,
+ExperienceReplayBuffer) and ReplayBuffer.prioritized (PrioritizedExperienceReplayBuffer, replay_buffers.py:104-141: priorities, their
+prefix sums, the draws, the importance-sampling weights and the priority updates all in device memory; a trainer's use_per selects it,
+the episode loop has no use for the switch and check_args refuses it).
 
 Divergences from the reference (INTEGRATION.md "Batched self-play"): a temperature-0 sample stores the real valid-action mask where the
-reference stores the visit counts (mcts.py:138); no prioritised replay, no tree reuse between steps, no per-episode shuffled priors; the
-draws are counter-based, not NumPy's global stream.
+reference stores the visit counts (mcts.py:138); no tree reuse between steps, no per-episode shuffled priors; the draws are counter-based,
+not NumPy's global stream.
 """
 from __future__ import annotations
 
@@ -101,6 +104,61 @@ def replay_draws(n: int, copies: int, seed: int, draw: int, committed_rows: np.n
     return rows, offs
 
 
+def per_uniforms(n: int, seed: int, draw: int) -> np.ndarray:
+    """The n uniforms of minibatch number `draw`, prioritised or uniform: counter i of subsequence REPLAY_STREAM + draw."""
+    return philox_uniform(np.arange(n, dtype=np.int64), REPLAY_STREAM + int(draw), seed)
+
+
+def per_mass(priorities, committed, alpha: float) -> np.ndarray:
+    """priorities ** alpha (replay_buffers.py:126) on the rows that are committed and hold a finite positive priority, 0 elsewhere."""
+    p = np.asarray(priorities, dtype=np.float64)
+    ok = np.asarray(committed, dtype=bool) & np.isfinite(p) & (p > 0)
+    mass = np.zeros(p.shape)
+    mass[ok] = p[ok] ** float(alpha)
+    return mass
+
+
+def per_probabilities(mass) -> np.ndarray:
+    """`probabilities /= probabilities.sum()` (:127)."""
+    mass = np.asarray(mass, dtype=np.float64)
+    return mass / mass.sum()
+
+
+def per_rows(mass, u) -> np.ndarray:
+    """np.random.choice(len(mass), p=probabilities) (:129) at the uniforms u: cdf = cumsum(p), cdf /= cdf[-1], cdf.searchsorted(u,
+    side="right"); past the last row with mass (rounding): that row; no mass at all: -1."""
+    mass, u = np.asarray(mass, dtype=np.float64), np.atleast_1d(np.asarray(u, dtype=np.float64))
+    if not mass.sum() > 0:
+        return np.full(u.shape, -1, dtype=np.int64)
+    cdf = np.cumsum(per_probabilities(mass))
+    cdf /= cdf[-1]
+    return np.minimum(np.searchsorted(cdf, u, side="right"), np.nonzero(mass > 0)[0][-1]).astype(np.int64)
+
+
+def per_weights(mass, rows, committed_count: int, beta: float) -> np.ndarray:
+    """(probabilities[rows] * L) ** -beta over its maximum, float32 (:135-136); NaN for a row of -1."""
+    rows = np.asarray(rows, dtype=np.int64)
+    if np.any(rows < 0):
+        return np.full(rows.shape, np.nan, dtype=np.float32)
+    w = (per_probabilities(mass)[rows] * committed_count) ** (-float(beta))
+    return np.array(w / w.max(), dtype=np.float32)
+
+
+def per_beta_step(beta: float, beta0: float, total_steps: int) -> float:
+    """PrioritizedExperienceReplayBuffer.step (:122-123)."""
+    return float(np.minimum(beta + (1 - beta0) / total_steps, 1))
+
+
+def per_update(priorities, indices, values) -> np.ndarray:
+    """`self.priorities[indices] = priorities` (:140-141) on a copy: the last occurrence of a repeated index wins, -1 is skipped."""
+    out = np.array(priorities, dtype=np.float64)
+    idx, val = np.asarray(indices, dtype=np.int64).reshape(-1), np.asarray(values, dtype=np.float64).reshape(-1)
+    for i, v in zip(idx, val):  # (in order, so that the last one stays)
+        if 0 <= i < len(out):
+            out[i] = v
+    return out
+
+
 def shift_planes(states: np.ndarray, offset) -> np.ndarray:
     """ReplicationPad2d(4) followed by the crop at (i, j) of the original size (RandomCrop with one offset for the whole 4-D batch)."""
     i, j = int(offset[0]), int(offset[1])
@@ -116,7 +174,8 @@ def check_args(hyper_params: Dict, meta_data: Dict, num_envs: int, capacity: Opt
     if not hyper_params.get("reset_mcts_each_step", True):
         raise ValueError("reset_mcts_each_step=False (tree reuse across steps) is not supported")
     if hyper_params.get("use_per", False):
-        raise ValueError("use_per=True (prioritised replay) is not supported")
+        raise ValueError("use_per=True is the trainer's switch, not the episode loop's: it is not supported here; draw prioritised "
+                         "minibatches with SelfPlay.replay.prioritized(...) (ReplayBuffer.prioritized)")
     if hyper_params.get("shuffle_prior_cov", False):
         raise ValueError("shuffle_prior_cov=True (per-episode shuffled priors) is not supported in budget mode")
     steps = int(meta_data.get("max_episode_steps", hyper_params.get("max_episode_steps", 0)))
@@ -175,6 +234,12 @@ class ReplayBuffer:
         """Device int64 indices of the committed rows, ascending."""
         return self.torch.nonzero(self.flags == COMMITTED).reshape(-1)
 
+
+    def prioritized(self, batch_size: int = 32, alpha: float = 0.75, beta0: float = 0.5, num_epochs: int = 3) -> "PrioritizedReplay":
+        """PrioritizedExperienceReplayBuffer (replay_buffers.py:104-141) over the rows committed now; reads their count from the device
+        once, as the reference reads len(self.data_file_paths)."""
+        return PrioritizedReplay(self, batch_size, alpha, beta0, num_epochs)
+
     def sample(self, batch_size: int, num_augmented_samples: int = 0, check_empty: bool = True):
         """(states [b (k+1), C, N, N] f32, policies [b (k+1), A] f32, values f64, rewards f64, valid_actions_msk [b (k+1), A] u8,
         indices i64 (ring rows), weights (ones, f64)) -- ExperienceReplayBuffer.sample with augment_random_crop: b = max(1, batch_size //
@@ -212,6 +277,90 @@ class ReplayBuffer:
         self.draws += 1
         self.last_offsets = offs
         return states, pol, val, rew, msk, index, torch.ones((rows,), dtype=torch.float64, device=dev)
+
+
+class PrioritizedReplay:
+    """PrioritizedExperienceReplayBuffer (replay_buffers.py:104-141) on the ring of a ReplayBuffer: rows drawn in proportion to
+    priority ** alpha, importance-sampling weights (P L) ** -beta over their maximum, priorities written back by update(), beta raised by
+    step().  Construction fixes the sampled set: the L rows committed then start at priority 1 / L, every other row at 0, so rows
+    committed later are not drawn (the reference's file list is fixed too) and a row that a later record re-opens drops out.  The
+    minibatch draws share the ring's draw count with ReplayBuffer.sample.  After construction nothing here reads the device from the host."""
+
+    def __init__(self, ring: ReplayBuffer, batch_size: int = 32, alpha: float = 0.75, beta0: float = 0.5, num_epochs: int = 3):
+        torch = self.torch = ring.torch
+        self.ring = ring
+        self.alpha, self.beta0, self.beta = float(alpha), float(beta0), float(beta0)
+        if not (0.0 <= self.alpha < float("inf")) or not (0.0 <= self.beta0 <= 1.0):
+            raise ValueError(f"alpha = {alpha} outside [0, inf) or beta0 = {beta0} outside [0, 1]")
+        self.sample_size = max(1, int(batch_size))  # (no augmented copies under PER, :114)
+        dev, cap = ring.flags.device, ring.capacity
+        own = ring._owner
+        self.priorities = torch.empty((cap,), dtype=torch.float64, device=dev)
+        self._cum = torch.empty((cap,), dtype=torch.float64, device=dev)
+        self._scratch = torch.empty(((cap + _ffi.IPP_REPLAY_SCAN_TILE - 1) // _ffi.IPP_REPLAY_SCAN_TILE,), dtype=torch.float64, device=dev)
+        count = torch.zeros((1,), dtype=torch.int64, device=dev)
+        _ffi.check(own._lib.ipp_replay_priority_reset(C.byref(own._sp), self.priorities.data_ptr(), count.data_ptr(), own.env.engine.stream))
+        self.committed = int(count.item())  # (the one read: len(self.data_file_paths))
+        if self.committed == 0:
+            raise ValueError("the replay buffer holds no committed sample yet (no episode has ended)")
+        self.total_steps = (self.committed // self.sample_size) * int(num_epochs)
+        if self.total_steps <= 0:
+            raise ValueError(f"total_steps = ({self.committed} committed rows // {self.sample_size}) x {num_epochs} epochs = 0: "
+                             f"the beta schedule has no step")
+        self.timing = None  # list of (start, drawn, end) events around the mass + draw and the gather launches while profiling
+
+    def __len__(self) -> int:
+        """Rows committed at construction (L; no device read)."""
+        return self.committed
+
+    def sample(self):
+        """(states [n, C, N, N] f32 or None, policies [n, A] f32, values f64, rewards f64, valid_actions_msk [n, A] u8, indices i64
+        (ring rows), weights f32), n = max(1, batch_size).  With no mass left (every sampled row re-opened): indices -1, NaN."""
+        torch, r = self.torch, self.ring
+        own, n = r._owner, self.sample_size
+        dev, sp, st = r.flags.device, C.byref(r._owner._sp), r._owner.env.engine.stream
+        states = torch.empty((n, r.channels, r.side, r.side), dtype=torch.float32, device=dev) if r.channels else None
+        pol = torch.empty((n, r.num_actions), dtype=torch.float32, device=dev)
+        msk = torch.empty((n, r.num_actions), dtype=torch.uint8, device=dev)
+        val = torch.empty((n,), dtype=torch.float64, device=dev)
+        rew = torch.empty((n,), dtype=torch.float64, device=dev)
+        index = torch.empty((n,), dtype=torch.int64, device=dev)
+        weights = torch.empty((n,), dtype=torch.float32, device=dev)
+        if self.timing is not None:
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            ev[0].record()
+        _ffi.check(own._lib.ipp_replay_mass(sp, self.priorities.data_ptr(), self.alpha, self._cum.data_ptr(), self._scratch.data_ptr(),
+                                            C.c_uint64(self._scratch.numel()), st))
+        _ffi.check(own._lib.ipp_replay_draw_per(sp, self.priorities.data_ptr(), self._cum.data_ptr(), self.alpha, self.beta, self.committed, n,
+                                                C.c_uint64(r.seed), C.c_uint64(REPLAY_STREAM + r.draws), index.data_ptr(),
+                                                weights.data_ptr(), st))
+        if self.timing is not None:
+            ev[1].record()
+        _ffi.check(own._lib.ipp_replay_gather_rows(sp, n, r.channels, r.side, r.planes.data_ptr() if r.channels else None, index.data_ptr(),
+                                                   states.data_ptr() if states is not None else None, pol.data_ptr(), msk.data_ptr(),
+                                                   val.data_ptr(), rew.data_ptr(), st))
+        if self.timing is not None:
+            ev[2].record()
+            self.timing.append(ev)
+        r.draws += 1
+        return states, pol, val, rew, msk, index, weights
+
+    def step(self):
+        """beta towards 1 by (1 - beta0) / total_steps (:122-123)."""
+        self.beta = per_beta_step(self.beta, self.beta0, self.total_steps)
+
+    def update(self, indices, priorities):
+        """priorities[indices] = priorities (:140-141; the caller adds the reference's 1e-8): device tensors stay on the device; the
+        last occurrence of a repeated index wins, -1 is skipped."""
+        torch, r = self.torch, self.ring
+        dev = r.flags.device
+        idx = torch.as_tensor(indices, device=dev).to(torch.int64).reshape(-1).contiguous()
+        val = torch.as_tensor(priorities, device=dev).to(torch.float64).reshape(-1).contiguous()
+        if idx.numel() != val.numel():
+            raise ValueError(f"{idx.numel()} indices, {val.numel()} priorities")
+        own = r._owner
+        _ffi.check(own._lib.ipp_replay_priority_update(C.byref(own._sp), self.priorities.data_ptr(), idx.data_ptr(), val.data_ptr(),
+                                                       int(idx.numel()), own.env.engine.stream))
 
 
 # ---------------------------------------------------------------------------------------------------- the loop

@@ -1,9 +1,12 @@
 """
 Throughput of the batched self-play loop (planning/mcts_zero/selfplay.py): samples/s and the split of a step into its phases --
 planes (ipp_feature_planes into the ring), search (DeviceMCTS, read-out on the device), record (ipp_selfplay_record), step (the fused
-budget step), commit (ipp_selfplay_commit) -- plus one replay minibatch (gather, ipp_replay_gather), from CUDA events around each phase.
+budget step), commit (ipp_selfplay_commit) -- plus one replay minibatch (gather, ipp_replay_gather), from CUDA events around each phase,
+and a prioritised-replay leg on the big ring: the PER minibatch (ipp_replay_mass + ipp_replay_draw_per, then ipp_replay_gather_rows)
+against the uniform minibatch (the committed prefix count + ipp_replay_gather) at the same n, alternating.
 
     python tools/selfplay_bench.py [--envs 4096] [--dim 50] [--sims 100] [--steps 8] [--warmup 2] [--planes-envs 8]
+                                   [--per-batch 1024] [--per-reps 20]
 
 The 4096-env run keeps no planes (a 50x50 plane is 25 MB per channel): its planes phase is reported as not measured; the planes phase
 and the gather kernel (CUDA events around the ipp_replay_gather launch alone, one minibatch of --batch rows with one augmented copy) are
@@ -47,6 +50,48 @@ def timed(sp, steps):
     return wall, split
 
 
+def per_leg(sp, n, reps):
+    """Prioritised against uniform minibatches of n rows on sp's ring, alternating, medians of `reps` (ms, CUDA events).  The rows
+    recorded so far are committed by hand (40-step episodes have not ended after a few steps: their value targets are not final, which
+    no timing depends on); the scan covers every ring row, committed or not."""
+    import numpy as np
+    import torch
+
+    from ipp_rl_amd.planning.mcts_zero.selfplay import COMMITTED, PENDING
+
+    r = sp.replay
+    r.flags[r.flags == PENDING] = COMMITTED
+    per = r.prioritized(batch_size=n)
+    rows = torch.nonzero(per.priorities > 0).reshape(-1)
+    per.update(rows, torch.rand(rows.numel(), dtype=torch.float64, device=rows.device) + 1e-8)  # (non-uniform priorities)
+    ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
+    for _ in range(3):
+        r.sample(n, check_empty=False)
+        per.sample()
+    uni_total, uni_kernel, per_total, per_draw, per_gather = [], [], [], [], []
+    for _ in range(reps):
+        r.timing, per.timing = [], []
+        a, b, c = ev(), ev(), ev()
+        a.record()
+        r.sample(n, check_empty=False)
+        b.record()
+        batch = per.sample()
+        idx = batch[5]
+        per.update(idx, batch[2].abs() + 1e-8)
+        c.record()
+        torch.cuda.synchronize()
+        uni_total.append(a.elapsed_time(b))
+        uni_kernel.append(r.timing[0][0].elapsed_time(r.timing[0][1]))
+        per_total.append(b.elapsed_time(c))
+        per_draw.append(per.timing[0][0].elapsed_time(per.timing[0][1]))
+        per_gather.append(per.timing[0][1].elapsed_time(per.timing[0][2]))
+    r.timing, per.timing = None, None
+    med = lambda v: float(np.median(v))  # noqa: E731
+    return {"ring_rows": r.capacity, "sampled_rows": len(per), "n": n, "reps": reps,
+            "uniform_minibatch_ms": med(uni_total), "uniform_gather_kernel_ms": med(uni_kernel),
+            "per_minibatch_and_update_ms": med(per_total), "per_mass_and_draw_ms": med(per_draw), "per_gather_rows_ms": med(per_gather)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=4096)
@@ -57,6 +102,8 @@ def main():
     ap.add_argument("--episode-steps", type=int, default=40)
     ap.add_argument("--planes-envs", type=int, default=8)
     ap.add_argument("--batch", type=int, default=96)
+    ap.add_argument("--per-batch", type=int, default=1024)
+    ap.add_argument("--per-reps", type=int, default=20)
     a = ap.parse_args()
     import torch
 
@@ -70,6 +117,7 @@ def main():
     wall, split = timed(sp, a.steps)
     ended = int((~torch.isnan(sp.episode_values)).sum().item())
     with_policy = int(sp.last["ok"].sum().item())
+    per = per_leg(sp, a.per_batch, a.per_reps)
     sp.close()
     del sp
     # the planes phase with planes in the ring (small batch, history 3, cost plane: 16 channels) and 3-step episodes, so that rows are
@@ -89,6 +137,7 @@ def main():
     out = {"envs": a.envs, "grid": a.dim, "sims": a.sims, "steps": a.steps, "samples_per_s": a.envs * a.steps / wall,
            "step_ms": 1e3 * wall / a.steps, "split_ms": split, "episodes_ended_last_step": ended,
            "roots_with_policy_last_step": with_policy, "gather_kernel_ms_small_batch": gather_ms, "gathered_rows": gathered_rows,
+           "prioritised_replay": per,
            "planes_ms_small_batch": {"envs": a.planes_envs, "planes": split_small["planes"], "record": split_small["record"]}}
     print(json.dumps(out))
 

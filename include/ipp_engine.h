@@ -873,6 +873,60 @@ int ipp_replay_gather_rows(const ipp_selfplay* sp, int32_t n, int32_t channels, 
 int ipp_replay_priority_update(const ipp_selfplay* sp, double* priority, const int64_t* index, const double* value, int32_t n,
                                void* stream);
 
+/* ---- Policy-value network ------------------------------------------------------------------------------------------------------
+ * Inference of the reference's PolicyValueNetwork (planning/mcts_zero/networks/policy_value_networks.py:12-69 on the layers of
+ * planning/common/layers.py) as a PLAN: a flat list of op records over one packed fp32 weight blob, built on the host by
+ * planning/mcts_zero/networks.py build_plan (every eval-mode BatchNorm folded into the conv in front of it, shared weights packed
+ * once; dropout, decoder and reward output left out, as predict() discards them).  Activations are channel-innermost
+ * ([n][H][W][C]) in three buffers (ids 0..2) the handle owns; the first conv reads ipp_feature_planes' [n][C][N][N] planes
+ * (src = IPP_PV_INPUT); pooled vectors live in slots 0 and 1.  Kernels: csrc/k_pvnet.h.
+ */
+#define IPP_PV_FP32 0 /* mfma_f32_16x16x4f32: a k-ordered f32 fma chain per output element                         */
+#define IPP_PV_BF16 1 /* mfma_f32_16x16x32_bf16: conv operands rounded to bfloat16 (nearest even), fp32 accumulate  */
+
+#define IPP_PV_OP_CONV   0 /* dst = act(conv(src) + bias [+ res]); kh x kw in {7x7, 3x3, 3x1, 1x3, 1x1}, stride 1 | 2; w [cout][kh][kw][cin] */
+#define IPP_PV_OP_MIX    1 /* MixGlobalContext's pooled part (layers.py:134-142), in place on src = dst: cin = G pooled channels of    */
+                           /* cout; w / b = the folded bn_layer's scale / shift [G], w2 = fc_layer [cout - G][2 G], b2 its bias        */
+#define IPP_PV_OP_POOL   2 /* GlobalPooling (layers.py:151-161): slot dst <- [mean | max] over the pixels of buffer src, 2 cin floats  */
+#define IPP_PV_OP_VALUE  3 /* ValueHead.head (layers.py:279) and invert_scaled_value_target (rewards.py:38-39) on slot src; w [2 cin]  */
+#define IPP_PV_OP_POLICY 4 /* PolicyHead.head and the masked softmax (layers.py:341-346) on the valid set; w [cout = A][2 cin]         */
+#define IPP_PV_ACT_NONE 0
+#define IPP_PV_ACT_RELU 1
+#define IPP_PV_ACT_SILU 2
+#define IPP_PV_INPUT (-1)
+
+typedef struct ipp_pvnet_op {
+    int32_t kind;
+    int32_t kh, kw, stride, pad_h, pad_w;
+    int32_t cin, cout;
+    int32_t hin, win, hout, wout;
+    int32_t src, dst, res; /* buffer ids (res: -1 = none); POOL: dst = slot; VALUE / POLICY: src = slot */
+    int32_t act;
+    int64_t w_off, b_off, w2_off, b2_off; /* offsets into the blob, in floats */
+} ipp_pvnet_op;
+
+/*
+ * `PolicyValueNetworkWrapper.__init__` / `load_checkpoint` for inference (policy_value_network_wrappers.py:21-29, :241-249): the plan and its
+ * weights [host] become a handle that owns the device weights and the activation buffers for max_batch samples.  An invalid plan
+ * (unknown op, buffer id out of range, shapes that do not chain, a weight offset beyond the blob) fails HERE with a message, never
+ * at launch.
+ */
+int ipp_pvnet_create(const ipp_pvnet_op* ops, int32_t n_ops, const float* weights, uint64_t n_floats, int32_t precision,
+                     int32_t max_batch, int32_t device, void** net);
+/* The hand-over after a training iteration (`self.network.load_state_dict`, :249): the same plan with new weights [host]. */
+int ipp_pvnet_set_weights(void* net, const float* weights, uint64_t n_floats, void* stream);
+/*
+ * `predict` (policy_value_network_wrappers.py:217-231) for n leaves: planes [dev] [n][C][N][N], valid_idx [dev] int32 [n][kmax]
+ * (-1 padded; an entry outside [0, A), A = the policy op's cout, counts as padding) -> prior [dev] double [n][kmax] =
+ * exp(log_policy) on the valid set (0 in padded slots and in rows without a valid
+ * action: equal to the dense masked softmax while a sample's logits span less than about 900), value [dev] double [n] = v^2 + 2 v.
+ * n above max_batch runs in chunks.  A handle serves ONE forward at a time (its activation buffers): callers on several streams order
+ * their calls (DevicePolicyValueNet does, with an event).  tap_op >= 0: tap_out [dev] float [n][cout][hout][wout] <- the output of that conv op.
+ */
+int ipp_pvnet_forward(void* net, const float* planes, int32_t n, const int32_t* valid_idx, int32_t kmax, double* prior, double* value,
+                      int32_t tap_op, float* tap_out, void* stream);
+int ipp_pvnet_destroy(void* net);
+
 #ifdef __cplusplus
 }
 #endif

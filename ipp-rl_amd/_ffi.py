@@ -200,6 +200,11 @@ PROTOTYPES = {
                                       _P, _P, _P]),
     "ipp_replay_gather_rows": (C.c_int, [C.POINTER(IppSelfPlay), C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ipp_replay_priority_update": (C.c_int, [C.POINTER(IppSelfPlay), _P, _P, _P, C.c_int32, _P]),
+    # (ops: an array of ipp_pvnet_op, planning/mcts_zero/networks.py IppPvnetOp)
+    "ipp_pvnet_create": (C.c_int, [_P, C.c_int32, _P, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P)]),
+    "ipp_pvnet_set_weights": (C.c_int, [_P, _P, C.c_uint64, _P]),
+    "ipp_pvnet_forward": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, _P, _P]),
+    "ipp_pvnet_destroy": (C.c_int, [_P]),
 }
 
 _lib = None

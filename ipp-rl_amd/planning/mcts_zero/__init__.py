@@ -1,1 +1,2 @@
 from .selfplay import PrioritizedReplay, ReplayBuffer, SelfPlay  # noqa: F401
+from .networks import DevicePolicyValueNet, PolicyValueNetwork  # noqa: F401

@@ -1,0 +1,203 @@
+"""
+GPU tests of the policy-value network's inference engine (DevicePolicyValueNet: csrc/k_pvnet.h through ipp_pvnet_*), against
+tests/golden/pvnet.npz recorded from the reference's PolicyValueNetwork.  The unit of every bound is d32 = max |ref32 - ref64| of the
+configuration and output: the reference's own fp32 rounding distance.
+
+F, the fp32 parity factor: twice the largest max |device - ref64| / d32 measured on an MI355X, rounded up to a power of two; it may
+not exceed 64 (folded BatchNorm plus another summation order cannot cost six bits: a larger ratio is a bug to find).  The measured
+ratios are recorded in DESIGN.md, "policy-value network".
+"""
+import numpy as np
+import pytest
+
+from tests import pvnet_cases as pc
+
+pytestmark = pytest.mark.gpu
+
+F = 4  # measured ratios: outputs <= 0.25, block outputs of (a) <= 1.64; 2 x 1.64 rounded up to a power of two
+assert F <= 64
+NAMES = ("a", "b", "c")
+_nets = {}
+
+
+def host(t):
+    return t.detach().cpu().numpy()
+
+
+def _net(name, precision="fp32", max_batch=128):
+    """One engine per (configuration, precision, max_batch), shared by the tests."""
+    from ipp_rl_amd.planning.mcts_zero import DevicePolicyValueNet
+
+    key = (name, precision, max_batch)
+    if key not in _nets:
+        case = pc.case(name)
+        _nets[key] = DevicePolicyValueNet(case["hp"], case["md"], case["state_dict"], side=case["cfg"]["side"], precision=precision,
+                                          max_batch=max_batch, device="cuda:0")
+    return _nets[key]
+
+
+def _run(net, planes, idx, **kw):
+    import torch
+
+    out = net.predict(torch.from_numpy(planes).cuda(), torch.from_numpy(idx).cuda(), **kw)
+    torch.cuda.synchronize()
+    return tuple(host(o) for o in out)
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_fp32_parity(name):
+    case = pc.case(name)
+    prior, value = _run(_net(name), case["planes"], case["valid_idx"])
+    r_p = np.abs(prior - case["prior64"]).max() / case["d32_prior"]
+    r_v = np.abs(value - case["value64"]).max() / case["d32_value"]
+    print(f"RATIO {name} fp32: prior {r_p:.3f} d32 (d32 {case['d32_prior']:.3g}), value {r_v:.3f} d32 (d32 {case['d32_value']:.3g})")
+    assert r_p <= F and r_v <= F
+
+
+def test_taps_of_every_block():
+    case = pc.case("a")
+    net, rows = _net("a"), list(pc.TAP_ROWS)
+    assert [b for b, _ in net.plan.blocks] == case["tap_names"]
+    worst = 0.0
+    for name, want, d32 in zip(case["tap_names"], case["taps64"], case["tap_d32"]):
+        _, _, tap = _run(net, case["planes"], case["valid_idx"], tap_op=net.plan.tap(name))
+        assert tap.shape[1:] == want.shape[1:], name
+        r = np.abs(tap[rows] - want).max() / d32
+        print(f"RATIO tap {name}: {r:.3f} d32 (d32 {d32:.3g})")
+        worst = max(worst, r)
+        assert r <= F, name
+    print(f"RATIO taps worst: {worst:.3f}")
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_batch_independence_bitwise(precision):
+    case = pc.case("a")
+    net = _net("a", precision)
+    prior, value = _run(net, case["planes"], case["valid_idx"])
+    for i in (0, 63, 64, 69):
+        p1, v1 = _run(net, case["planes"][i:i + 1], case["valid_idx"][i:i + 1])
+        assert np.array_equal(p1[0], prior[i]) and v1[0] == value[i], (precision, i)
+
+
+def test_chunking_bitwise():
+    case = pc.case("a")
+    big = _run(_net("a", max_batch=128), case["planes"], case["valid_idx"], tap_op=_net("a").plan.tap("encoder.block4"))
+    small = _run(_net("a", max_batch=16), case["planes"], case["valid_idx"], tap_op=_net("a").plan.tap("encoder.block4"))
+    for a, b in zip(big, small):
+        assert np.array_equal(a, b)
+
+
+def test_load_state_dict_changes_the_network():
+    import torch
+
+    from ipp_rl_amd.planning.mcts_zero import DevicePolicyValueNet
+    from ipp_rl_amd.planning.mcts_zero.networks import build_plan, run_plan_numpy
+
+    case = pc.case("c")
+    fx = pc.fixture()
+    import json
+    names, shapes = json.loads(str(fx["c_keys"])), json.loads(str(fx["c_shapes"]))
+    other = {k: torch.from_numpy(v) for k, v in pc.draw_state_dict(names, shapes, 909).items()}
+    net = DevicePolicyValueNet(case["hp"], case["md"], case["state_dict"], side=9, max_batch=8, device="cuda:0")
+    before = _run(net, case["planes"], case["valid_idx"])
+    net.load_state_dict(other)
+    prior, value = _run(net, case["planes"], case["valid_idx"])
+    plan, w = build_plan(case["hp"], case["md"], other, 9, dtype=np.float64)
+    want_p, want_v = run_plan_numpy(plan, w, case["planes"], case["valid_idx"])
+    assert np.abs(want_v - case["value64"]).max() > 1e-3  # another network
+    assert np.abs(value - before[1]).max() > 1e-3
+    unit_p, unit_v = 16 * case["d32_prior"], 16 * case["d32_value"]
+    r_p, r_v = np.abs(prior - want_p).max() / unit_p, np.abs(value - want_v).max() / unit_v
+    print(f"RATIO c reloaded: prior {r_p:.3f} value {r_v:.3f} (unit 16 d32)")
+    assert r_p <= F and r_v <= F
+    net.close()
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_padding_and_empty_rows(precision):
+    for name in NAMES:
+        case = pc.case(name)
+        prior, value = _run(_net(name, precision), case["planes"], case["valid_idx"])
+        K = (case["valid_idx"] >= 0).sum(axis=1)
+        assert K[0] == 1 and K[1] == pc.KMAX and K[2] == 0
+        assert np.all(prior[2] == 0) and np.all(np.isfinite(value))
+        assert np.all(prior[case["valid_idx"] < 0] == 0)
+        assert np.abs(prior[K > 0].sum(axis=1) - 1).max() <= 1e-6
+        assert prior[0, 0] == 1.0
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_bf16_against_the_emulation(name):
+    from ipp_rl_amd.planning.mcts_zero.networks import build_plan, run_plan_numpy
+
+    case = pc.case(name)
+    plan, w = build_plan(case["hp"], case["md"], case["state_dict"], case["cfg"]["side"])
+    emu_p, emu_v = run_plan_numpy(plan, w, case["planes"], case["valid_idx"], round_operands="bf16")
+    prior, value = _run(_net(name, "bf16"), case["planes"], case["valid_idx"])
+    for what, dev, emu, ref, d32 in (("prior", prior, emu_p, case["prior64"], case["d32_prior"]), ("value", value, emu_v, case["value64"], case["d32_value"])):
+        e_dev, e_emu = np.abs(dev - ref).max(), np.abs(emu - ref).max()
+        print(f"RATIO {name} bf16 {what}: device {e_dev:.3g}, emulation {e_emu:.3g}, bound {2 * e_emu + F * d32:.3g}")
+        assert e_dev <= 2 * e_emu + F * d32, what
+    assert not np.array_equal(value, _run(_net(name), case["planes"], case["valid_idx"])[1])  # (the bf16 path ran)
+
+
+def test_search_and_selfplay_with_the_network():
+    import torch
+
+    from ipp_rl_amd import EngineConfig
+    from ipp_rl_amd.planning.mcts_zero import DevicePolicyValueNet, PolicyValueNetwork, SelfPlay
+    from ipp_rl_amd.planning.mcts_zero.device_mcts import DeviceMCTS
+    from ipp_rl_amd.planning.mcts_zero.networks import build_plan, run_plan_numpy
+    from tests.test_hip_selfplay import _params
+
+    # the smallest self-play setup: a 40 x 40 split field, history 1 in position mode with the cost plane: planes [n, 6, 1600, 1600]
+    cfg, B = EngineConfig(x_dim=40, y_dim=40, simulation="split_random_field"), 4
+    hp, md = _params(num_mcts_simulations=8)
+    net_hp = dict(input_channels=6, num_channels=8, dropout=0.0, use_silu=True, num_encoder_res_blocks=7, use_separable_conv_layers=True,
+                  use_global_context_mixing=True, num_global_pooling_channels=4, num_policy_head_conv_bn_blocks=1, num_value_head_conv_bn_blocks=1,
+                  mask_policy_head=True, use_reward_target=False, use_autoencoder=False)
+    net_md = dict(md, num_grid_cells=cfg.n_cells)
+    torch.manual_seed(3)
+    module = PolicyValueNetwork(net_hp, net_md).eval()
+    sd = module.state_dict()
+    net = DevicePolicyValueNet(net_hp, net_md, sd, side=cfg.n_cells, max_batch=8, device="cuda:0")
+    kept = []
+
+    def infer(batch):
+        reply = net.infer(batch)
+        if not kept and len(batch["node"]) > 1:
+            kept.append(tuple(t[:4].clone() for t in (batch["planes"], batch["valid_idx"], reply[0], reply[1])))
+        return reply
+
+    sp = SelfPlay(cfg, B, hp, md, infer=infer, seed=5, sims_in_flight=2)
+    env, mcts = sp.env, sp.mcts  # DeviceMCTS(engine, hp, md, infer, feature_planes=True): 4 roots x 8 simulations
+    assert isinstance(mcts, DeviceMCTS) and mcts.plane_spec is not None and mcts.plane_spec.channels == 6
+    out = mcts.search_device(sp._roots, env.prev, env.budget, sp._temps, sp.tie_u, depth=0, root_history=env.history_entries())
+    torch.cuda.synchronize()
+    assert np.all(host(out["ok"]) == 1) and kept
+    for pol in out["policy"]:
+        np.testing.assert_allclose(host(pol).sum(axis=1), 1.0, atol=1e-9)
+    # one wave's reply (its first rows: a plane is 1600 x 1600) against the plan in NumPy, by the rule of test_fp32_parity; the unit is this
+    # network's own fp32 rounding distance on these rows: the restated module in float32 against float64 on the CPU
+    planes, idx, prior, value = (host(t) for t in kept[0])
+    assert np.isfinite(planes).all()
+    rows = len(planes)
+    plan, w = build_plan(net_hp, net_md, sd, cfg.n_cells, dtype=np.float64)
+    want_p, want_v = run_plan_numpy(plan, w, planes, idx)
+    dense = torch.zeros((rows, net.plan.num_actions), dtype=torch.float64)
+    for r in range(rows):
+        dense[r, idx[r][idx[r] >= 0]] = 1.0
+    with torch.no_grad():
+        o32 = module.float()(torch.from_numpy(planes), dense.float())
+        o64 = module.double()(torch.from_numpy(planes).double(), dense)
+    inv = lambda v: v * v + 2 * v  # noqa: E731
+    d32_p = float((torch.exp(o32[0]).double() - torch.exp(o64[0])).abs().max())
+    d32_v = float((inv(o32[1].double()) - inv(o64[1])).abs().max())
+    e_p, e_v = np.abs(prior - want_p).max(), np.abs(value - want_v).max()
+    print(f"RATIO search wave: prior {e_p / d32_p:.3f} d32 ({d32_p:.3g}), value {e_v / d32_v:.3f} d32 ({d32_v:.3g})")
+    assert e_p <= F * d32_p and e_v <= F * d32_v
+    for _ in range(2):
+        sp.step()
+    torch.cuda.synchronize()
+    assert not torch.isnan(sp.replay.policy).any()
+    net.close()

@@ -203,6 +203,15 @@ int ipp_engine_create_prior(const ipp_config* cfg, int32_t kind, int device, voi
 int ipp_engine_destroy(void* engine);
 int ipp_engine_info(void* engine, ipp_info* out /*[host]*/);
 
+/* Which ground-truth generator ipp_reset(white_noise) / ipp_generate_grf run on this engine's grid (decided at creation from the grid
+ * size and the IPP_GRF_FFT / IPP_GRF_HARTLEY switches): *kind = IPP_GRF_GEN_*; *param = the padded size in 16-row tiles (HARTLEY, FFT),
+ * the spectrum rows per LDS chunk (DFT), 0 (CONV).  Tests and A/B runs: that a switch was seen. */
+#define IPP_GRF_GEN_CONV 0    /* circular convolution + normalisation kernel: odd n, n > 256, non-square grids fail at the call */
+#define IPP_GRF_GEN_DFT 1     /* half-spectrum DFT (k_grf_dft.h) */
+#define IPP_GRF_GEN_HARTLEY 2 /* four fp64 GEMMs with the Hartley matrix (k_grf_hartley.h) */
+#define IPP_GRF_GEN_FFT 3     /* fast Hartley transforms in LDS, draws its own noise (k_grf_fft.h) */
+int ipp_grf_generator(void* engine, int32_t* kind /*[host]*/, int32_t* param /*[host]*/);
+
 /*
  * Episode reset of `n` env slots: mean <- 0.5, covariance <- prior, rank <- 0, ground truth <- gt / GRF.
  * Replaces: Mapping.init_priors GP branch (mapping/mappings.py:235-261) incl. shuffle_prior_cov draws

@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("IPP_HIP_LIB") or os.path.join(_HERE, "lib", "libipp_hip.so")  # override: A/B builds only
 
 IPP_DENSE, IPP_FACTOR = 0, 1
+IPP_GRF_GEN_CONV, IPP_GRF_GEN_DFT, IPP_GRF_GEN_HARTLEY, IPP_GRF_GEN_FFT = 0, 1, 2, 3
 IPP_PRIOR_MATERN32, IPP_PRIOR_MATERN12, IPP_PRIOR_MATERN52, IPP_PRIOR_RBF = 0, 1, 2, 3
 IPP_COV_ONLY, IPP_PREDICT_ONLY, IPP_ADAPTIVE, IPP_USE_FLIGHT_TIME, IPP_GIVEN_OBSERVATION, IPP_UPDATE_PREV = 1, 2, 4, 8, 16, 32
 IPP_BUDGET, IPP_RESET_ON_DONE = 64, 128
@@ -130,6 +131,7 @@ PROTOTYPES = {
     "ipp_engine_create_prior": (C.c_int, [C.POINTER(IppConfig), C.c_int32, C.c_int, _P, C.c_uint64, C.POINTER(_P)]),
     "ipp_engine_destroy": (C.c_int, [_P]),
     "ipp_engine_info": (C.c_int, [_P, C.POINTER(IppInfo)]),
+    "ipp_grf_generator": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ipp_reset": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
     "ipp_reset_episode": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "ipp_score_actions": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_uint32, _P, _P, _P]),

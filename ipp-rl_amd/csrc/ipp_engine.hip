@@ -997,7 +997,8 @@ int ipp_engine_create_prior(const ipp_config* cfg, int32_t kind, int device, voi
         HIP_TRY(hipMemcpy(v.grf_h, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
         const int n = cfg->x_dim;
         e->grf_dft = (n % 2 == 0) && n >= 4 && n <= 256;  // odd n: the reference's amp is not even (ground_truths.py:8-11)
-        if (e->grf_dft && n <= 128) {
+        const bool hartley = !(sw.grf_hartley && *sw.grf_hartley == 0);  // A/B and tests: k_grf_dft as before the GEMM form existed
+        if (e->grf_dft && n <= 128 && hartley) {
             const int tt = (n + 15) / 16;
             std::vector<double> hp, amp;
             bool ok = grf_hartley_tables_host(n, 16 * tt, cfg->cluster_radius, hp, amp);
@@ -1063,6 +1064,15 @@ int ipp_engine_destroy(void* engine) {
         for (auto& ev : e->ev_prep) (void)hipEventDestroy(ev);
     }
     delete e;
+    return 0;
+}
+
+int ipp_grf_generator(void* engine, int32_t* kind, int32_t* param) {  // (the order of launch_grf)
+    Engine* e = as_engine(engine);
+    if (!e || !kind || !param) return fail(-1, "null argument");
+    if (e->grf_tt > 0) { *kind = e->grf_fft ? IPP_GRF_GEN_FFT : IPP_GRF_GEN_HARTLEY; *param = e->grf_tt; }
+    else if (e->grf_dft) { *kind = IPP_GRF_GEN_DFT; *param = e->grf_kc; }
+    else { *kind = IPP_GRF_GEN_CONV; *param = 0; }
     return 0;
 }
 

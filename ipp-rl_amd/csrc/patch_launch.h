@@ -36,6 +36,7 @@ struct Switches {
     std::optional<int> rect_tree = env_int("IPP_RECT_TREE");      // tree steps on rectangle tiles
     std::optional<int> tree_split = env_int("IPP_TREE_SPLIT");    // smallest tree launch that runs k_tree_prepare + k_tree_gain (0: never)
     std::optional<int> grf_fft = env_int("IPP_GRF_FFT");          // 0: the GEMM form of the Hartley ground truths
+    std::optional<int> grf_hartley = env_int("IPP_GRF_HARTLEY");  // 0: no Hartley form at all: even n <= 128 run k_grf_dft
 };
 
 // One instantiation of k_step_patch<NW, KPN, MINW, SPLIT, RJN, BUD> (k_tree_patch<NW, RJN>) and what a launch of it is given.

@@ -525,6 +525,13 @@ class IPPEngine:
         self._keep_planes = (entries, me, mm)
         return out
 
+    def grf_generator(self):
+        """(kind, param) of the ground-truth generator this engine runs (ipp_grf_generator): kind = _ffi.IPP_GRF_GEN_*; param = 16-row
+        tiles of the padded size (HARTLEY, FFT), spectrum rows per LDS chunk (DFT), 0 (CONV)."""
+        kind, param = C.c_int32(-1), C.c_int32(-1)
+        _ffi.check(self._lib.ipp_grf_generator(self._h, C.byref(kind), C.byref(param)))
+        return int(kind.value), int(param.value)
+
     def generate_grf(self, white_noise, out=None, stream=None):
         """white noise [n, N] -> normalised GRF [n, N] in a caller tensor (no env slot touched)."""
         torch = _torch()

@@ -32,13 +32,20 @@ from .fields import check_hotspot, field_kind
 INIT_ACTION = (2.0, 2.0, 14.0)  # planning/missions.py:69
 
 
-def philox_uniform(counter, subsequence, seed: int) -> np.ndarray:
-    """Philox4x32-10 of (counter, subsequence) under key `seed`, first output word as a uniform in (0, 1): the host copy of the device's
-    draw of a start budget (ipp_common.h, budget_start).  counter / subsequence: int arrays (broadcast)."""
+def _as_u64(x) -> np.ndarray:
+    """Integers (Python ints up to 2^64 - 1, negative ones as their two's complement, or arrays) as uint64."""
+    if isinstance(x, (int, np.integer)):
+        return np.asarray(int(x) & (2 ** 64 - 1), dtype=np.uint64)
+    a = np.asarray(x)
+    return a if a.dtype == np.uint64 else a.astype(np.int64).astype(np.uint64)
+
+
+def philox_words(counter, subsequence, seed: int):
+    """Philox4x32-10 (Salmon et al., SC'11) of the 128-bit counter (counter, subsequence) under the 64-bit key `seed`: the four 32-bit
+    output words as uint64 arrays, the host copy of the ten rounds of philox_normal4 (csrc/k_misc.h).  counter / subsequence: ints or
+    int arrays (broadcast; negative values count as their 64-bit two's complement)."""
     m32 = np.uint64(0xFFFFFFFF)
-    q = np.asarray(counter, dtype=np.int64).astype(np.uint64)
-    sub = np.asarray(subsequence, dtype=np.int64).astype(np.uint64)
-    q, sub = np.broadcast_arrays(q, sub)
+    q, sub = np.broadcast_arrays(_as_u64(counter), _as_u64(subsequence))
     c = [q & m32, q >> np.uint64(32), sub & m32, sub >> np.uint64(32)]
     k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64((seed >> 32) & 0xFFFFFFFF)
     with np.errstate(over="ignore"):
@@ -48,7 +55,41 @@ def philox_uniform(counter, subsequence, seed: int) -> np.ndarray:
             c = [(p1 >> np.uint64(32)) ^ c[1] ^ k0, p1 & m32, (p0 >> np.uint64(32)) ^ c[3] ^ k1, p0 & m32]
             k0 = (k0 + np.uint64(0x9E3779B9)) & m32
             k1 = (k1 + np.uint64(0xBB67AE85)) & m32
-    return (c[0].astype(np.float64) + 0.5) * (1.0 / 4294967296.0)
+    return c
+
+
+def philox_uniform(counter, subsequence, seed: int) -> np.ndarray:
+    """Philox4x32-10 of (counter, subsequence) under key `seed`, first output word as a uniform in (0, 1): the host copy of the device's
+    draw of a start budget (ipp_common.h, budget_start).  counter / subsequence: int arrays (broadcast)."""
+    return (philox_words(counter, subsequence, seed)[0].astype(np.float64) + 0.5) * (1.0 / 4294967296.0)
+
+
+def philox_normal4_ref(counter, subsequence, seed: int) -> np.ndarray:
+    """The four standard normals of every counter, float64 [..., 4]: the DEFINITION of the device's philox_normal4 (csrc/k_misc.h), not
+    its instructions.  Uniforms as the device forms them, in float32: u = (float(word) + 0.5f) * 2^-32; from there in float64, Box-Muller
+    of the pairs (word 0, word 1) and (word 2, word 3): rad = sqrt(-2 log(max(u0, 1e-30))), angle 2 pi u1, elements
+    (rad0 cos0, rad0 sin0, rad1 cos1, rad1 sin1)."""
+    words = philox_words(counter, subsequence, seed)
+    u = [((w.astype(np.float32) + np.float32(0.5)) * np.float32(2.0 ** -32)).astype(np.float64) for w in words]
+    out = np.empty(words[0].shape + (4,), dtype=np.float64)
+    for h in range(2):
+        rad = np.sqrt(-2.0 * np.log(np.maximum(u[2 * h], 1e-30)))
+        ang = 2.0 * np.pi * u[2 * h + 1]
+        out[..., 2 * h] = rad * np.cos(ang)
+        out[..., 2 * h + 1] = rad * np.sin(ang)
+    return out
+
+
+def philox_normal_rows_ref(planes: int, row_ids, row_len: int, seed: int, subsequence: int, row_offset: int = 0) -> np.ndarray:
+    """What ipp_fill_normal_rows writes, float64 [planes, rows, row_len]: element c of row j of plane p is normal c % 4 of
+    counter (row_ids[j] + row_offset) * ceil(row_len / 4) + c // 4 in subsequence `subsequence` + p."""
+    qpr = (row_len + 3) // 4
+    rid = np.array([(int(r) + int(row_offset)) & (2 ** 64 - 1) for r in row_ids], dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        q = rid[:, None] * np.uint64(qpr) + np.arange(qpr, dtype=np.uint64)[None, :]
+    sub = np.array([(int(subsequence) + p) & (2 ** 64 - 1) for p in range(planes)], dtype=np.uint64)
+    nrm = philox_normal4_ref(q[None, :, :], sub[:, None, None], seed)
+    return nrm.reshape(planes, len(rid), 4 * qpr)[:, :, :row_len]
 
 
 def start_budget(initial_budget: float, shuffle_budget: bool, seed: int, global_env_ids, episode) -> np.ndarray:

@@ -192,9 +192,9 @@ int ipp_engine_create(const ipp_config* cfg, int device, void* arena /*[dev]*/, 
  * ConstantKernel(sigma^2) * Matern(length_scale, nu=mapping.nu) prior of Mapping.init_priors, evaluated through an
  * unfitted GaussianProcessRegressor (mapping/mappings.py:236-261, config/example.yaml:27 nu) for the four nu that
  * sklearn evaluates in closed form.  window_rows is checked against the kind's own decay: the smallest R with
- * sigma^2 k(R resolution; l_max) <= 1e-6 (ipp_min_window_rows_prior; 14 / 10 / 8 rows for nu = 0.5 / 1.5 / 2.5 of the
- * example config with fixed_prior = 1, 16 / 12 / 10 without).  RBF takes the Matern 3/2 rule (10 / 12): the RBF gain columns
- * reach further than its prior (ipp_engine.hip, window_bound).  An unknown kind fails (ipp_last_error).
+ * sigma^2 k(R resolution; l_max) <= 1e-6 (ipp_min_window_rows_prior; 14 / 10 rows for nu = 0.5 / 1.5 of the
+ * example config with fixed_prior = 1, 16 / 12 without).  Matern 5/2 and RBF take the Matern 3/2 rule (10 / 12): their gain
+ * columns reach further than their priors (ipp_engine.hip, window_bound).  An unknown kind fails (ipp_last_error).
  */
 int ipp_min_window_rows_prior(const ipp_config* cfg, int32_t kind, int32_t* rows /*[host]*/);
 int ipp_engine_arena_bytes_prior(const ipp_config* cfg, int32_t kind, uint64_t* bytes /*[host]*/);

@@ -3,13 +3,21 @@ CPU checks of the batched feature planes (ipp_feature_planes): the entry record 
 spec, rejected specs and arguments, and a NumPy restatement of generate_input_feature_planes (planning/common/features.py:83-151)
 against the reference's outputs recorded in tests/golden/planes.npz (gen_plane_golden.py) at 1e-12.  The restatement is the
 definition the device kernel is tested against in tests/test_hip_feature_planes.py.
+
+The second half builds the fp64 states those device tests compare with: seeded walks replayed through the dense Kalman chain of
+oracle/ipp_oracle.py (oracle_history), the requests made of them, and the mask threshold of each request (pick_threshold), whose
+margin is checked here for every case so that no cell's mask can differ on the device.
 """
 import ctypes
 import math
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
+
+from oracle import ipp_oracle as orc
+from tests.test_prior_kernels_host import prior_matrix
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "planes.npz")
@@ -214,3 +222,191 @@ def test_vec_env_feature_history_needs_budget_mode():
         VecIPPEnv.check_feature_history(-1, budget=200.0)
     VecIPPEnv.check_feature_history(3, budget=200.0)
     VecIPPEnv.check_feature_history(0, budget=None)
+
+
+# ----------------------------------------------------------------------------- fp64 states for the device comparisons
+START = np.array([2.0, 2.0, 14.0])  # planning/missions.py:69
+UAV = {"max_v": 2.0, "max_a": 2.0}
+ALTS = (6.0, 8.0, 9.0, 12.0, 14.0)  # m = 1, 9, 9, 4, 9 measurements; rf = 2 above 10 m
+# The 8-step walks take a seeded order of these: 7 x 9 + 4 columns, so the ranks pass 32 and 64 (the chunks of k_feature_planes'
+# column loop) and end at 67, whatever the seed.  6 m (one measurement) is drawn in the tree and state-plane walks.
+WALK_ALTS = (8.0, 8.0, 9.0, 9.0, 12.0, 14.0, 14.0, 14.0)
+KF = 0.5
+MARGIN = 1e-4  # the device diagonal and mean are within 1e-5 of fp64 and KF <= 1: a cell's score moves by < 2e-5
+PREFIX_STEPS = (6, 3, 1)
+BUDGETS = (0.9, 0.7, 0.45, 0.2, 0.05)
+INF = float("inf")
+# name: (dim, nu, seed).  The seeds were chosen on the CPU so that every request below has margin >= MARGIN and a mask that is
+# neither empty nor full for every entry (test_reference_masks_are_nontrivial_with_margin).  The patch layout needs an even
+# x_dim > 2 * window_rows + 13: 40 for the 10-row windows of nu = 1.5, 2.5 and inf, 42 for nu = 0.5 (14 rows).
+HISTORY_CASES = {
+    "exact10": (10, 1.5, 5), "exact11": (11, 1.5, 8), "exact": (20, 1.5, 2), "band": (20, 1.5, 2), "patch": (40, 1.5, 56),
+    "exact11-nu0.5": (11, 0.5, 39), "exact11-nu2.5": (11, 2.5, 3), "exact11-nuinf": (11, INF, 8),
+    "patch-nu0.5": (42, 0.5, 66), "patch-nu2.5": (40, 2.5, 11), "patch-nuinf": (40, INF, 4),
+}
+TREE_CASES = {"band": (20, 1.5, 1), "patch": (40, 1.5, 1)}
+TREE_ENV_STEPS, TREE_CHAIN, TREE_FORK = 3, 6, 2  # nodes 0 .. 5 in a chain below the env, node 6 a second child of node 1
+# ipp_state_plane (tests/test_hip_features.py): name: (dim, nu); the walk of that test (seed 21, waypoints over the whole grid)
+PLANE_CASES = {"factor-0": (20, 1.5), "patch40": (40, 1.5), "factor-0-nu2.5": (20, 2.5)}
+
+
+def pick_threshold(scores):
+    """(thr, margin) for the reference's mean + kf * diag(P) of every entry of a request: the midpoint and half the width of the
+    widest gap between consecutive sorted values inside the middle half of their range [min + (max - min) / 4, max - (max - min)
+    / 4].  (Of the range, not of the rank order: after a few steps on a 40 x 40 grid three quarters of the cells still hold the
+    prior variance and the initial mean, so the values between the quartiles are one point and have no gap.)"""
+    v = np.sort(np.concatenate([np.ravel(x) for x in scores]))
+    q = 0.25 * (v[-1] - v[0])
+    w = v[(v >= v[0] + q) & (v <= v[-1] - q)]
+    assert w.size >= 2, "fewer than two scores inside the middle half"
+    gaps = np.diff(w)
+    k = int(np.argmax(gaps))
+    return float(0.5 * (w[k] + w[k + 1])), float(0.5 * gaps[k])
+
+
+def oracle_history(dim, nu, white, actions, eps, tree=()):
+    """Replays `actions` (with the ground truth of `white` and the measurement noise `eps`, the first m of every row) through
+    the dense fp64 chain from the prior of `nu` and keeps P after every step: P[k] / ranks[k] = the state and the number of
+    factor columns after k steps.  tree: (node id, parent id or None = the final env state, action) in creation order, chained
+    with predict_step; nodes[id] = that node's P, fov[id] = its footprint."""
+    cfg = orc.OracleConfig(x_dim=dim, y_dim=dim)
+    st = orc.env_reset(cfg, white)
+    if nu != 1.5:
+        st.P = prior_matrix(nu, dim)
+    P, ranks = [st.P], [0]
+    for a, e in zip(actions, eps):
+        m = orc.num_measurements(orc.project_fov(cfg, a), orc.resolution_factor(a))
+        orc.env_step(cfg, st, a, e[:m])
+        P.append(st.P)
+        ranks.append(ranks[-1] + m)
+    nodes, fov = {}, {}
+    for nid, parent, a in tree:
+        nodes[nid] = orc.predict_step(cfg, st.P if parent is None else nodes[parent], START, a)[1]
+        fov[nid] = orc.project_fov(cfg, a)
+    return SimpleNamespace(cfg=cfg, st=st, P=P, ranks=ranks, nodes=nodes, fov=fov)
+
+
+def seeded_walk(dim, seed, steps=len(WALK_ALTS), alts=None, spread=None):
+    """White noise, waypoints over cell centres within `spread` cells of the grid's centre (no footprint is clipped there),
+    altitudes (a seeded order of WALK_ALTS, or draws from `alts`), measurement noise and an fp32 mean for the mask.  That mean
+    is uniform in [0, 4): wider than KF times the prior variance (0.91), so that the scores of observed and of unobserved cells
+    overlap in the middle of the range and a threshold there splits every entry, the bare prior included."""
+    rs = np.random.RandomState(seed)
+    white = rs.normal(size=(dim, dim))
+    spread = min(4, dim // 2 - 3) if spread is None else spread
+    cells = dim // 2 + rs.randint(-spread, spread + 1, size=(steps, 2))
+    alt = rs.permutation(WALK_ALTS)[:steps] if alts is None else rs.choice(alts, size=steps)
+    actions = np.column_stack([RES * cells[:, 0] + 0.5 * RES, RES * cells[:, 1] + 0.5 * RES, alt])
+    eps = rs.normal(size=(steps, 9))
+    mask_mean = rs.uniform(0, 4, size=dim * dim).astype(np.float32)
+    return SimpleNamespace(white=white, actions=actions, eps=eps, mask_mean=mask_mean)
+
+
+def history_case(name):
+    """Section-2 request of one case: (walk, history, request); the request's entries newest first -- the current state, the
+    prefixes at the ranks recorded before steps 6, 3 and 1, and rank 0 (the bare prior)."""
+    dim, nu, seed = HISTORY_CASES[name]
+    w = seeded_walk(dim, seed)
+    h = oracle_history(dim, nu, w.white, w.actions, w.eps)
+    T = len(w.actions)
+    idx = [T] + list(PREFIX_STEPS) + [0]
+    req = SimpleNamespace(states=[h.P[k] for k in idx], ranks=[-1] + [h.ranks[k] for k in idx[1:]], paths=[None] * len(idx),
+                          positions=[w.actions[k - 1] if k else START for k in idx], budgets=list(BUDGETS))
+    return w, h, req
+
+
+def tree_case(name):
+    """Section-3 request: 3 env steps, a chain of 6 nodes and a sibling of node 2; entries: the paths of depth 6 and 3, the
+    sibling, depth 1, the root."""
+    dim, nu, seed = TREE_CASES[name]
+    w = seeded_walk(dim, seed, steps=TREE_ENV_STEPS + TREE_CHAIN + 1, alts=ALTS, spread=3)
+    env_a, tree_a = w.actions[:TREE_ENV_STEPS], w.actions[TREE_ENV_STEPS:]
+    tree = [(d, d - 1 if d else None, tree_a[d]) for d in range(TREE_CHAIN)] + [(TREE_CHAIN, TREE_FORK - 1, tree_a[TREE_CHAIN])]
+    h = oracle_history(dim, nu, w.white, env_a, w.eps[:TREE_ENV_STEPS], tree)
+    paths = [list(range(6)), [0, 1, 2], [0, 1, TREE_CHAIN], [0], []]
+    req = SimpleNamespace(states=[h.nodes[p[-1]] if p else h.st.P for p in paths], ranks=[-1] * len(paths), paths=paths,
+                          positions=[tree_a[p[-1]] if p else env_a[-1] for p in paths], budgets=list(BUDGETS))
+    w.tree = tree
+    return w, h, req
+
+
+def plane_walk(dim, seed=21, steps=6):
+    """The walk of test_state_plane_of_engine_slots_vs_oracle: waypoints over the whole grid, altitudes 5 .. 14 m."""
+    rs = np.random.RandomState(seed)
+    white = rs.normal(size=(dim, dim))
+    actions, eps = [], []
+    for _ in range(steps):
+        actions.append(np.array([4.0 * rs.randint(0, dim) + 2.0, 4.0 * rs.randint(0, dim) + 2.0, float(rs.randint(5, 15))]))
+        eps.append(rs.normal(size=9))
+    return SimpleNamespace(white=white, actions=np.array(actions), eps=np.array(eps), other_mean=rs.uniform(0, 1, size=(dim, dim)))
+
+
+def dense_edge_case(seed=5, n=110, slots=2):
+    """Covariances for the largest plane k_feature_planes keeps in LDS (110 cells: 48 400 + 112 + 16 736 = 65 248 of 65 536
+    bytes), exact in fp32, and an fp32 mean."""
+    rs = np.random.RandomState(seed)
+    mats = []
+    for _ in range(slots):
+        A = rs.normal(size=(n, n))
+        mats.append((A @ A.T / n).astype(np.float32).astype(np.float64))
+    return mats, rs.uniform(0, 1, size=n).astype(np.float32)
+
+
+def request_scores(states, mean):
+    return [np.asarray(mean, dtype=np.float64).ravel() + KF * np.diag(P) for P in states]
+
+
+def check_margin(states, mean, what):
+    """pick_threshold of a request, with the two conditions that make the device comparison total."""
+    scores = request_scores(states, mean)
+    thr, margin = pick_threshold(scores)
+    assert margin >= MARGIN, f"{what}: margin {margin:.3g}"
+    for k, sc in enumerate(scores):
+        assert 0 < int((sc >= thr).sum()) < sc.size, f"{what}: entry {k} has a trivial mask"
+    return thr, margin
+
+
+@pytest.mark.parametrize("name", list(HISTORY_CASES))
+def test_reference_masks_are_nontrivial_with_margin(name):
+    w, h, req = history_case(name)
+    assert h.ranks[-1] == 67 and min(h.ranks[1:]) < 32 < max(h.ranks[:-1]) < 64 < h.ranks[-1]
+    assert 0 < min(req.ranks[1:4]) < 32 < max(req.ranks[1:4]) < 64 and req.ranks[4] == 0
+    m1 = check_margin(req.states, w.mask_mean, f"{name} mask_mean")[1]
+    m2 = check_margin(req.states, h.st.mean, f"{name} mask_env")[1]
+    print(f"{name}: margins {m1:.3g} (mask_mean) {m2:.3g} (mask_env)")
+    dim, nu, _ = HISTORY_CASES[name]
+    if nu != 1.5:  # the rank-0 entry is the prior of this nu, and no other kind's plane is within the tolerance of it
+        assert np.array_equal(req.states[-1], prior_matrix(nu, dim))
+        assert np.max(np.abs(state_plane(req.states[-1]) - state_plane(prior_matrix(1.5, dim)))) > 1e-2
+
+
+@pytest.mark.parametrize("name", list(TREE_CASES))
+def test_reference_tree_masks_are_nontrivial_with_margin(name):
+    w, h, req = tree_case(name)
+    check_margin(req.states, w.mask_mean, f"{name} tree mask_mean")
+    check_margin(req.states, h.st.mean, f"{name} tree mask_env")
+    # plane_diag looks a cell up in the deepest node of the path that holds it: two nodes of the deepest path share cells
+    def cells(f):
+        return {(x, y) for x in range(f[0], f[1] + 1) for y in range(f[2], f[3] + 1)}
+    assert any(cells(h.fov[a]) & cells(h.fov[b]) for a in range(TREE_CHAIN) for b in range(a))
+    alts = set(w.actions[TREE_ENV_STEPS:, 2])
+    assert 6.0 in alts and alts & {12.0, 14.0} and alts & {8.0, 9.0}  # m = 1, rf = 2 and rf = 1 among the tree's steps
+
+
+@pytest.mark.parametrize("name", list(PLANE_CASES))
+def test_reference_state_plane_masks_are_nontrivial_with_margin(name):
+    dim, nu = PLANE_CASES[name]
+    w = plane_walk(dim)
+    h = oracle_history(dim, nu, w.white, w.actions, w.eps)
+    check_margin([h.st.P], h.st.mean, f"{name} own mean")
+    check_margin([h.st.P], w.other_mean, f"{name} other mean")
+
+
+def test_reference_dense_edge_masks_are_nontrivial_with_margin():
+    mats, mean = dense_edge_case()
+    check_margin(mats, mean, "dense 10 x 11")
+
+
+def test_pick_threshold():
+    thr, margin = pick_threshold([np.array([0.0, 0.3, 0.35, 0.6, 1.0]), np.array([0.3, 0.7])])
+    assert (thr, margin) == pytest.approx((0.475, 0.125), abs=1e-15)  # [0.25, 0.75] holds 0.3, 0.3, 0.35, 0.6, 0.7

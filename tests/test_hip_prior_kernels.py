@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 TOL = 1e-5
 UAV = {"max_v": 2.0, "max_a": 2.0}
 D = 6
-MIN_FIXED = {0.5: 14, 1.5: 10, 2.5: 8, float("inf"): 10}
+MIN_FIXED = {0.5: 14, 1.5: 10, 2.5: 10, float("inf"): 10}
 
 
 def host(t):

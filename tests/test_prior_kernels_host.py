@@ -67,12 +67,12 @@ def min_rows(kind, c):
 
 
 def test_min_window_rows_of_every_kind():
-    """The smallest windows of the example prior at 4 m cells (fixed prior / shuffled): nu = 0.5 14/16, 1.5 10/12, 2.5 8/10,
-    inf 10/12 (the Matern 3/2 rule); kind 0 is the old entry point; other priors follow a search of the same 1e-6 bound."""
+    """The smallest windows of the example prior at 4 m cells (fixed prior / shuffled): nu = 0.5 14/16, 1.5 10/12, 2.5 10/12,
+    inf 10/12 (both by the Matern 3/2 rule); kind 0 is the old entry point; other priors follow a search of the same 1e-6 bound."""
     from ipp_rl_amd import _ffi
 
     lib = _ffi.load()
-    want = {_ffi.IPP_PRIOR_MATERN12: (14, 16), _ffi.IPP_PRIOR_MATERN32: (10, 12), _ffi.IPP_PRIOR_MATERN52: (8, 10),
+    want = {_ffi.IPP_PRIOR_MATERN12: (14, 16), _ffi.IPP_PRIOR_MATERN32: (10, 12), _ffi.IPP_PRIOR_MATERN52: (10, 12),
             _ffi.IPP_PRIOR_RBF: (10, 12)}
     for kind, (fixed, shuffled) in want.items():
         assert min_rows(kind, host_config(fixed_prior=1)) == fixed
@@ -82,7 +82,7 @@ def test_min_window_rows_of_every_kind():
         c = host_config(fixed_prior=fp)
         assert lib.ipp_min_window_rows(ctypes.byref(c), ctypes.byref(old)) == 0
         assert old.value == min_rows(_ffi.IPP_PRIOR_MATERN32, c)
-    nus = {_ffi.IPP_PRIOR_MATERN12: 0.5, _ffi.IPP_PRIOR_MATERN32: 1.5, _ffi.IPP_PRIOR_MATERN52: 2.5, _ffi.IPP_PRIOR_RBF: 1.5}
+    nus = {_ffi.IPP_PRIOR_MATERN12: 0.5, _ffi.IPP_PRIOR_MATERN32: 1.5, _ffi.IPP_PRIOR_MATERN52: 1.5, _ffi.IPP_PRIOR_RBF: 1.5}
     for sv, ls, res in ((1.0, 2.0, 1.0), (3.5, 10.0, 4.0), (0.3, 1.5, 2.0)):
         for fp in (0, 1):
             l_max = ls * (1.0 if fp else 1.2)
@@ -122,7 +122,7 @@ def test_arena_bytes_of_kind_0_and_narrow_windows():
         assert lib.ipp_engine_arena_bytes(ctypes.byref(c), ctypes.byref(a)) == 0
         assert lib.ipp_engine_arena_bytes_prior(ctypes.byref(c), _ffi.IPP_PRIOR_MATERN32, ctypes.byref(b)) == 0
         assert a.value == b.value
-    for kind, rows in ((_ffi.IPP_PRIOR_MATERN12, 14), (_ffi.IPP_PRIOR_MATERN52, 8), (_ffi.IPP_PRIOR_RBF, 10)):
+    for kind, rows in ((_ffi.IPP_PRIOR_MATERN12, 14), (_ffi.IPP_PRIOR_MATERN52, 10), (_ffi.IPP_PRIOR_RBF, 10)):
         c = host_config(window_rows=rows, fixed_prior=1)
         assert lib.ipp_engine_arena_bytes_prior(ctypes.byref(c), kind, ctypes.byref(a)) == 0, lib.ipp_last_error()
         c.window_rows = rows - 1

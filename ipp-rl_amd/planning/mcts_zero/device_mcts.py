@@ -18,7 +18,8 @@ streams on the device (statistically equivalent, not NumPy's streams), and the n
 
     infer(batch) -> (prior or None, value)
         batch: dict of device tensors for the n pending leaves of this wave -- "root" (env slot), "node", "depth",
-        "previous_action" [n, 3], "budget" [n], "valid_idx" [n, kmax] (ascending action indices, -1 padded), "K" [n]
+        "previous_action" [n, 3], "budget" [n], "valid_idx" [n, kmax] (ascending action indices, -1 padded), "K" [n] (>= 1: a leaf
+        without a valid action is worth 0 and is not asked about, mcts.py:199-201; stats["inferences"] counts the leaves asked about)
         prior: [n, kmax] float64 probabilities on the valid sets (need not be normalised) or None = uniform
         value: [n] float64 tensor or a float
     infer=None: uniform priors, value `leaf_value` (the stub of the benchmarks).
@@ -264,11 +265,12 @@ class DeviceMCTS(VectorMCTS):
             self.stats["device_steps"] += n
             self.stats["launches"] += 1 if ahead else 0
             if n_pending:
-                self._expand(lib, tp, b, R, W, root_env, stream, sim, prev0, budget0)
-                self.stats["inferences"] += n_pending
+                self.stats["inferences"] += self._expand(lib, tp, b, R, W, root_env, stream, sim, prev0, budget0)
             _ffi.check(lib.ipp_mcts_backup(tp, int(w), stream))
             sim += w
         err = b["err"].cpu().numpy()
+        if self.infer is None:  # (stub: every leaf with a valid action was expanded once and counts as one inference, like the host drivers')
+            self.stats["inferences"] += int((b["n_flags"] & 1).sum().item())
         if err[0] or err[1] or err[3]:
             raise RuntimeError(f"device tree search ran out of room (nodes, device nodes, kmax) = {err[0], err[1], err[3]}: "
                                f"raise nodes_per_root / the engine's node_capacity")
@@ -447,13 +449,19 @@ class DeviceMCTS(VectorMCTS):
         seed = C.c_uint64((self.seed * 0x9E3779B97F4A7C15 + 12345) & (2 ** 64 - 1))
         if self.infer is None:
             _ffi.check(lib.ipp_mcts_expand(tp, None, None, self.leaf_value, 0, self.alpha, self.eps, seed, stream))
-            return
+            return 0  # (counted at the end of the search)
         # network: valid sets first, then the replies scattered into [R W] slot order
         _ffi.check(lib.ipp_mcts_expand(tp, None, None, 0.0, 1, self.alpha, self.eps, seed, stream))
         cnt = b["counts"][:R].to(torch.int64)
         slot = torch.arange(W, device=cnt.device)[None, :] < cnt[:, None]  # [R, W] pending slots
-        g = torch.nonzero(slot.reshape(-1)).reshape(-1)
-        nodes = b["pend_node"].reshape(-1)[g].to(torch.int64)
+        # a leaf without a valid action returns 0 BEFORE the network is asked (mcts.py:199-201): it is no inference and not in the batch
+        # (the slots that are not pending hold stale node numbers: clamped for the look-up, masked by `slot`)
+        pend = b["pend_node"].reshape(-1).to(torch.int64).clamp_(0, b["n_k"].numel() - 1)
+        g = torch.nonzero(slot.reshape(-1) & (b["n_k"][pend] > 0)).reshape(-1)
+        if g.numel() == 0:
+            _ffi.check(lib.ipp_mcts_expand(tp, None, None, 0.0, 0, self.alpha, self.eps, seed, stream))  # (clears the sets-only marks)
+            return 0
+        nodes = pend[g]
         batch = dict(root=root_env[(g // W)], node=nodes, depth=b["pend_depth"].reshape(-1)[g],
                      previous_action=b["pend_prev"].reshape(-1, 3)[g], budget=b["pend_budget"].reshape(-1)[g],
                      valid_idx=b["t_idx"][nodes], K=b["n_k"][nodes])
@@ -475,6 +483,7 @@ class DeviceMCTS(VectorMCTS):
         _ffi.check(lib.ipp_mcts_expand(tp, pr_all.data_ptr() if pr_all is not None else None, v_ptr, v_const, 0, self.alpha, self.eps,
                                        seed, stream))
         self._keep_infer = (pr_all, v_all)
+        return int(g.numel())
 
     def _policies(self, b, R, npr, prev0, budget0, temperature, deploy_time, rngs, roots, as_arrays=False):
         """get_policy (mcts.py:83-143) from the root rows: on the device (ipp_mcts_policy), or through VectorMCTS._policy_sparse /

@@ -511,16 +511,13 @@ def stub_value(mask):
     return 0.05 * float(int(mask.sum()) % 7) + 0.3
 
 
-def gen_mcts():
+def _record_mcts(cases, **hyper_over):
+    """The reference's search on each case (stubbed inference queues) with the example configuration's hyper-parameters, `hyper_over`
+    on top: the arrays of the mcts*.npz fixtures."""
     import planning.mcts_zero.mcts as ref_mcts
     from planning.common.features import EpisodeHistory
 
     out = {}
-    cases = [
-        # name, grid, adaptive, root steps, sims, altitudes (min, max, spacing), budget, horizon, seed
-        ("a5", 5, False, 2, 96, (8, 14, 6), 30.0, 3, 3),
-        ("b10", 10, True, 3, 80, (8, 14, 6), 40.0, 5, 5),
-    ]
     for name, dim, adaptive, root_steps, sims, (amin, amax, aspc), budget, horizon, seed in cases:
         params = load_params(dim, dim)
         gm, sensor, sim, mapping = build(params, seed=seed)
@@ -543,6 +540,7 @@ def gen_mcts():
             prev = a
         hyper = dict(params["experiment"]["missions"][0]["hyper_params"])
         hyper.update(num_mcts_simulations=sims, non_blocking_read=False)
+        hyper.update(hyper_over)
         scenario = {"value_threshold": 0.4, "interval_factor": 0} if adaptive else None
         meta = {"budget": budget, "initial_budget": budget, "episode_horizon": horizon, "min_altitude": amin,
                 "max_altitude": amax, "altitude_spacing": aspc, "uav_specifications": uav, "scenario_info": scenario}
@@ -583,7 +581,23 @@ def gen_mcts():
     out["hyper_gamma"] = hyper["gamma"]
     out["hyper_dirichlet_alpha"] = hyper["dirichlet_alpha"]
     out["hyper_dirichlet_eps"] = hyper["dirichlet_eps"]
-    save("mcts", **out)
+    return out
+
+
+def gen_mcts():
+    save("mcts", **_record_mcts([
+        # name, grid, adaptive, root steps, sims, altitudes (min, max, spacing), budget, horizon, seed
+        ("a5", 5, False, 2, 96, (8, 14, 6), 30.0, 3, 3),
+        ("b10", 10, True, 3, 80, (8, 14, 6), 40.0, 5, 5),
+    ]))
+
+
+def gen_mcts_decayed():
+    """One search with the hyper-parameters training reaches, not the ones it starts from: the discount below 1 and the Dirichlet
+    shape at the floor of its schedule (config/example.yaml: dirichlet_alpha decays from 1.0 by 0.8 per iteration down to 0.3), so
+    that the noise comes from the shape < 1 branch of the gamma sampler.  Written to its own file: mcts.npz stays as recorded."""
+    save("mcts_decayed", **_record_mcts([("d10", 10, True, 3, 80, (8, 14, 6), 40.0, 5, 6)],
+                                        gamma=0.9, dirichlet_alpha=0.3, dirichlet_eps=0.25))
 
 
 def gen_mcts_mission():
@@ -918,6 +932,7 @@ def main():
     gen_costs()
     gen_features()
     gen_mcts()
+    gen_mcts_decayed()
     gen_mcts_mission()
     gen_call_trace()
     shapes = sorted(set(RESIZE_CALLS))

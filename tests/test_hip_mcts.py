@@ -60,11 +60,10 @@ def meta_from(g, name):
             "scenario_info": {"value_threshold": 0.4, "interval_factor": 0} if adaptive else None}
 
 
-@pytest.mark.parametrize("name", ["a5", "b10"])
-def test_search_reproduces_the_reference_mcts(golden, name):
+def _check_search_against_the_reference(g, name):
+    """One recorded search of the reference (fixture g, case `name`) rebuilt by BatchedMCTS with the fixture's hyper-parameters."""
     from ipp_rl_amd.planning.mcts_zero.mcts import BatchedMCTS
 
-    g = golden("mcts")
     eng = build_root(g, name)
     mcts = BatchedMCTS(eng, hyper_from(g, g[f"{name}_sims"]), meta_from(g, name), stub_infer)
     np.random.seed(int(g[f"{name}_seed"]))  # the reference draws from the global legacy stream: same calls, same order
@@ -89,6 +88,19 @@ def test_search_reproduces_the_reference_mcts(golden, name):
     assert mcts.stats["device_steps"] <= mcts.stats["revisits"] + mcts.stats["new_visits"]
     # the root env slot is untouched by the search
     assert np.max(np.abs(host(eng.read_diag(0)) - g[f"{name}_root_diag"])) < TOL
+
+
+@pytest.mark.parametrize("name", ["a5", "b10"])
+def test_search_reproduces_the_reference_mcts(golden, name):
+    _check_search_against_the_reference(golden("mcts"), name)
+
+
+def test_search_reproduces_the_reference_mcts_with_decayed_hyper_parameters(golden):
+    """The same comparison with the hyper-parameters training reaches (tests/golden/gen_golden.py::gen_mcts_decayed): discount 0.9 and
+    Dirichlet shape 0.3 -- the reference's own search with val = reward + gamma value' below 1 and noise from numpy's shape < 1 branch."""
+    g = golden("mcts_decayed")
+    assert float(g["hyper_gamma"]) == 0.9 and float(g["hyper_dirichlet_alpha"]) == 0.3 and float(g["hyper_dirichlet_eps"]) == 0.25
+    _check_search_against_the_reference(g, "d10")
 
 
 def test_batched_roots_equal_single_root_searches_and_parallel_simulations():

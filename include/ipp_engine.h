@@ -936,6 +936,37 @@ int ipp_pvnet_forward(void* net, const float* planes, int32_t n, const int32_t* 
                       int32_t tap_op, float* tap_out, void* stream);
 int ipp_pvnet_destroy(void* net);
 
+/*
+ * The training iteration's loss (policy_value_network_wrappers.py:116-154 with the static methods at :251-261) for one minibatch,
+ * values and gradients in ONE launch; no handle.  All pointers [dev]: logits float [n][A] = policy_head.head's output BEFORE the
+ * mask, target_policy float [n][A], valid_msk uint8 [n][A], value float [n] = value_head.head's output, reward float [n] or null,
+ * target_value / target_reward double [n] (rounded to float first, as torch.FloatTensor does at :100-101; target_reward and
+ * grad_reward null exactly when reward is null), weights double [n].  Per row i, in fp64 after the float loads:
+ *     z'_j = z_j - (1 - m_j) 1000 (a shift, not a mask: layers.py:343-344), lp = z' - logsumexp(z') over all A entries,
+ *     pl = -sum t_j lp_j m_j (:257), H = -sum exp(lp_j) lp_j (:253), vl = (v - tv)^2, rl = (r - tr)^2 (:261),
+ *     total = (pc pl + vc vl + rc rl - ec H) w (:122-149); the batch loss is the mean of the totals (:154).
+ * stats double [n][6] = pl, vl, rl (0 without reward), H, total, |tv - v| / |tv| (:265).  grad_logits float [n][A], grad_value and
+ * grad_reward float [n] = the gradient of the batch mean: with p = exp(lp), T = sum t_j m_j,
+ *     (w / n) (pc (-t_j m_j + T p_j) + ec p_j (lp_j + H)),   (w / n) 2 vc (v - tv),   (w / n) 2 rc (r - tr).
+ * No floating-point atomics: two calls give the same bits.  n == 0 launches nothing.
+ */
+int ipp_pvnet_loss(const float* logits, const float* target_policy, const uint8_t* valid_msk, const float* value, const float* reward,
+                   const double* target_value, const double* target_reward, const double* weights, int32_t n, int32_t num_actions,
+                   double policy_coeff, double value_coeff, double reward_coeff, double entropy_coeff, double* stats, float* grad_logits,
+                   float* grad_value, float* grad_reward, int32_t device, void* stream);
+/*
+ * `clip_grad_norm_(parameters, max_norm, 2)` and `optimizer.step()` of torch.optim.SGD with dampening 0 and no Nesterov (:167-172) on
+ * ONE flat vector; no handle.  params, grads, momentum_buf [dev] float [n]; in fp64 from the float loads, one rounding per stored value:
+ *     norm = sqrt(sum g^2), coef = min(1, max_norm / (norm + 1e-6)), g' = coef g + weight_decay p, buf = momentum buf + g'
+ *     (a zeroed buffer reproduces torch's first step), p -= lr buf.
+ * norm_out [dev] double [1] <- the norm before clipping; a non-finite norm propagates, as torch's default does.  Two launches: partial
+ * sums of squares per workgroup into scratch ([dev] double, IPP_PVNET_SGD_SCRATCH doubles always suffice), then their sum in a fixed
+ * order and the update: deterministic.  n == 0 launches nothing.
+ */
+#define IPP_PVNET_SGD_SCRATCH 1024
+int ipp_pvnet_sgd_step(float* params, const float* grads, float* momentum_buf, int64_t n, double lr, double momentum, double weight_decay,
+                       double max_norm, double* norm_out, double* scratch, uint64_t scratch_doubles, int32_t device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@ IPP_BUDGET_STREAM = 3 << 40
 # Philox subsequence bases of the self-play draws (ipp_selfplay_record / _commit, ipp_replay_gather)
 IPP_SP_ACTION_STREAM, IPP_SP_INIT_STREAM, IPP_SP_TIE_STREAM, IPP_SP_ARGMAX_STREAM, IPP_REPLAY_STREAM = (4 << 40, 5 << 40, 6 << 40, 7 << 40,
                                                                                                        8 << 40)
+IPP_PVNET_SGD_SCRATCH = 1024  # doubles of scratch that always suffice for ipp_pvnet_sgd_step (one per workgroup of its first launch)
 IPP_REPLAY_SCAN_TILE = 2048  # ring rows per workgroup of ipp_replay_mass's prefix sum (its scratch: one double per tile)
 IPP_FIELD_GRF, IPP_FIELD_HOTSPOT, IPP_FIELD_SPLIT = 0, 1, 2
 STATUS_OK, STATUS_CHOL_FALLBACK, STATUS_NOT_PD, STATUS_RANK_FULL, STATUS_BAD_FOOTPRINT = 0, 1, 2, 3, 4
@@ -207,6 +208,11 @@ PROTOTYPES = {
     "ipp_pvnet_set_weights": (C.c_int, [_P, _P, C.c_uint64, _P]),
     "ipp_pvnet_forward": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, _P, _P]),
     "ipp_pvnet_destroy": (C.c_int, [_P]),
+    # (the trainer's calls, csrc/k_train.h: added without an ABI bump, like the prioritised-replay calls)
+    "ipp_pvnet_loss": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
+                                 _P, _P, _P, _P, C.c_int32, _P]),
+    "ipp_pvnet_sgd_step": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, C.c_uint64,
+                                     C.c_int32, _P]),
 }
 
 _lib = None

@@ -1,6 +1,7 @@
 // The policy-value network's inference engine (include/ipp_engine.h "Policy-value network"): a validated plan of op records, the
 // packed weights on the device (fp32, and their bf16 rounding for the bf16 path), three activation buffers sized for max_batch,
 // and a forward that launches one kernel per op (csrc/k_pvnet.h).  A translation unit of its own: nothing here touches the env engine.
+// The trainer's two calls (ipp_pvnet_loss, ipp_pvnet_sgd_step: csrc/k_train.h) live here too; they need no handle.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -10,6 +11,7 @@
 
 #include "../../include/ipp_engine.h"
 #include "k_pvnet.h"
+#include "k_train.h"
 
 namespace ipp { int set_error(int code, const char* msg); }
 
@@ -228,6 +230,50 @@ int ipp_pvnet_forward(void* handle, const float* planes, int32_t n, const int32_
         }
         PV_TRY(hipGetLastError());
     }
+    return 0;
+}
+
+int ipp_pvnet_loss(const float* logits, const float* target_policy, const uint8_t* valid_msk, const float* value, const float* reward,
+                   const double* target_value, const double* target_reward, const double* weights, int32_t n, int32_t num_actions,
+                   double policy_coeff, double value_coeff, double reward_coeff, double entropy_coeff, double* stats, float* grad_logits,
+                   float* grad_value, float* grad_reward, int32_t device, void* stream) {
+    if (n < 0) return ipp::set_error(-1, "ipp_pvnet_loss: n < 0");
+    if (num_actions < 1) return ipp::set_error(-1, "ipp_pvnet_loss: num_actions < 1");
+    if (!logits || !target_policy || !valid_msk || !value || !target_value || !weights || !stats || !grad_logits || !grad_value)
+        return ipp::set_error(-1, "ipp_pvnet_loss: null argument");
+    if ((reward == nullptr) != (target_reward == nullptr) || (reward == nullptr) != (grad_reward == nullptr))
+        return ipp::set_error(-1, "ipp_pvnet_loss: reward, target_reward and grad_reward are given together or not at all");
+    if (n == 0) return 0;
+    PV_TRY(hipSetDevice(device));
+    pvt::LossArgs a;
+    a.n = n; a.A = num_actions;
+    a.logits = logits; a.target_policy = target_policy; a.valid_msk = valid_msk; a.value = value; a.reward = reward;
+    a.target_value = target_value; a.target_reward = target_reward; a.weights = weights;
+    a.pc = policy_coeff; a.vc = value_coeff; a.rc = reward_coeff; a.ec = entropy_coeff;
+    a.stats = stats; a.grad_logits = grad_logits; a.grad_value = grad_value; a.grad_reward = grad_reward;
+    hipLaunchKernelGGL(pvt::k_pv_loss, dim3((unsigned)n), dim3(pvt::kThreads), 0, reinterpret_cast<hipStream_t>(stream), a);
+    PV_TRY(hipGetLastError());
+    return 0;
+}
+
+int ipp_pvnet_sgd_step(float* params, const float* grads, float* momentum_buf, int64_t n, double lr, double momentum, double weight_decay,
+                       double max_norm, double* norm_out, double* scratch, uint64_t scratch_doubles, int32_t device, void* stream) {
+    static_assert(pvt::kSgdMaxBlocks == IPP_PVNET_SGD_SCRATCH, "scratch bound");
+    if (n < 0) return ipp::set_error(-1, "ipp_pvnet_sgd_step: n < 0");
+    if (!params || !grads || !momentum_buf || !norm_out || !scratch) return ipp::set_error(-1, "ipp_pvnet_sgd_step: null argument");
+    const int blocks = pvt::sgd_blocks(n);
+    if (scratch_doubles < (uint64_t)blocks) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "ipp_pvnet_sgd_step: scratch of %llu doubles, %d needed", (unsigned long long)scratch_doubles, blocks);
+        return ipp::set_error(-1, buf);
+    }
+    if (n == 0) return 0;
+    PV_TRY(hipSetDevice(device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(pvt::k_sgd_partial, dim3(blocks), dim3(pvt::kThreads), 0, s, grads, (long long)n, scratch);
+    hipLaunchKernelGGL(pvt::k_sgd_update, dim3(blocks), dim3(pvt::kThreads), 0, s, params, grads, momentum_buf, (long long)n, lr, momentum,
+                       weight_decay, max_norm, (const double*)scratch, norm_out);
+    PV_TRY(hipGetLastError());
     return 0;
 }
 

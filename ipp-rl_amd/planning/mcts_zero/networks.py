@@ -3,8 +3,8 @@ The policy-value network of the MCTS-zero loop: the trainable module, its infere
 
   PolicyValueNetwork     what planning/mcts_zero/networks/policy_value_networks.py and planning/common/layers.py of the reference
                          compute, restated: same submodule and parameter names (a reference checkpoint loads with strict=True), same
-                         forward (x, valid_actions_msk) -> (log_policy, value, reward, decoder).  The training-side object and the
-                         oracle of the tests; nothing on the hot path uses it.
+                         forward (x, valid_actions_msk) -> (log_policy, value, reward, decoder).  The training-side object (training.Trainer
+                         trains it through forward_logits) and the oracle of the tests; the search's hot path does not use it.
   build_plan             an eval-mode network as a flat list of op records and ONE packed weight blob: every BatchNorm folded into
                          the conv in front of it (running statistics, affine, its own eps), weights the network shares packed once.
                          Dropout, the decoder and the reward output are not planned: predict() discards them
@@ -214,8 +214,11 @@ class _PolicyHead(_HeadTrunk):
         self.head = nn.Sequential(nn.Linear(2 * channels, actions))
         self.output_fn = nn.LogSoftmax(dim=1)
 
+    def logits(self, x):
+        return self.head(self.trunk(x))
+
     def forward(self, x, valid_actions_msk):
-        logits = self.head(self.trunk(x))
+        logits = self.logits(x)
         if self.mask_policy_head:
             logits = logits - (1 - valid_actions_msk) * 1000
         return self.output_fn(logits)
@@ -244,6 +247,13 @@ class PolicyValueNetwork(nn.Module):
         log_policy = self.policy_head(x, valid_actions_msk)
         value, reward = self.value_head(x)
         return log_policy, value, reward, (self.decoder(x) if self.hyper_params["use_autoencoder"] else None)
+
+    def forward_logits(self, x):
+        """(logits, value, reward, decoder): forward without the mask and the LogSoftmax, what ipp_pvnet_loss takes (training.Trainer)."""
+        x = self.encoder(x)
+        logits = self.policy_head.logits(x)
+        value, reward = self.value_head(x)
+        return logits, value, reward, (self.decoder(x) if self.hyper_params["use_autoencoder"] else None)
 
 
 # ------------------------------------------------------------------------------------------------------------------ the plan

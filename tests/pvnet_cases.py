@@ -1,6 +1,7 @@
 """
-The policy-value network cases of tests/golden/pvnet.npz, shared by the generator (tests/golden/gen_pvnet_golden.py) and the tests
-(test_pvnet_host.py, test_hip_pvnet.py): the three configurations, and the DRAWS of their weights and planes.
+The policy-value network cases of tests/golden/pvnet.npz (a, b, c) and tests/golden/pvnet_edges.npz (d, e, f, g), shared by the
+generator (tests/golden/gen_pvnet_golden.py) and the tests (test_pvnet_host.py, test_hip_pvnet.py): the configurations, and the DRAWS
+of their weights and planes.
 
 A network's weights are not stored in the fixture: configuration (c) alone has 1.5 MB of them, above what one committed file may hold.
 The fixture records the state_dict as names, shapes, a seed and a CRC-32 per tensor, and draw_state_dict() reproduces the tensors
@@ -14,8 +15,10 @@ from functools import lru_cache
 
 import numpy as np
 
-KMAX = 37
-FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pvnet.npz")
+KMAX = 37  # of a, b and c; a configuration's own is kmax(name)
+_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+FIXTURE = os.path.join(_GOLDEN, "pvnet.npz")
+EDGE_FIXTURE = os.path.join(_GOLDEN, "pvnet_edges.npz")
 # the smallest configurations at which a class of mistake still shows:
 #   a: the reference's full default schedule down to 1x1 pixels, a batch above one 64-row tile, an input channel count that is no multiple of anything
 #   b: odd side, the plain residual path with its biased 1x1 identity convs, two altitude levels
@@ -25,7 +28,50 @@ CONFIGS = {
     "b": dict(side=13, input_channels=7, channels=16, pooled=4, blocks=4, separable=False, mixing=False, silu=False, heads=(2, 1), levels=2, n=5, seed=202),
     "c": dict(side=9, input_channels=3, channels=48, pooled=16, blocks=7, separable=True, mixing=True, silu=True, heads=(1, 2), levels=1, n=5, seed=303),
 }
+# ... and past one 64-channel tile of k_pv_conv, one pixel at the head pools and one pass of the 256-thread loops of k_pv_heads and
+# k_pv_mix ("Policy-value network", has the table of which configuration reaches which edge; test_pvnet_host.py asserts it):
+#   d: 72 channels: two output-channel tiles, the second 8 columns wide; no K a multiple of 32; a 3x3 map at the head pools; G = 24
+#   e: the shipped network's channel, input and pooled counts: two full tiles, every K a multiple of 32, a 2x2 map at the head pools
+#   f: 264 channels: five tiles, a head pool over >= 256 channels, 260 context channels in the mix, three altitude levels
+#   g: 136 channels: a head pool over 129..255 channels, three tiles, the last 8 columns wide
+# kmax = 300: the policy head's loops over the slots run a second pass.  `seed` is where the generator STARTS: it keeps the first seed
+# at which a float32 NumPy run of the plan lies within 2 d32 of ref64 (gen_pvnet_golden.py), and the fixture's {x}_seed is the one kept.
+EDGE_CONFIGS = {
+    "d": dict(side=24, input_channels=5, channels=72, pooled=24, blocks=3, separable=True, mixing=True, silu=True, heads=(2, 2), levels=1, n=8, seed=404, kmax=300),
+    "e": dict(side=32, input_channels=16, channels=128, pooled=32, blocks=4, separable=True, mixing=True, silu=True, heads=(2, 2), levels=1, n=8, seed=505, kmax=300),
+    "f": dict(side=12, input_channels=3, channels=264, pooled=4, blocks=4, separable=False, mixing=True, silu=False, heads=(2, 1), levels=3, n=8, seed=606, kmax=300),
+    "g": dict(side=12, input_channels=4, channels=136, pooled=8, blocks=2, separable=False, mixing=False, silu=False, heads=(1, 1), levels=3, n=8, seed=707, kmax=300),
+}
+EDGE_NAMES = tuple(EDGE_CONFIGS)
+CONFIGS.update(EDGE_CONFIGS)
 TAP_ROWS = (0, 1, 2, 3, 31, 32, 62, 63, 64, 65, 68, 69)  # the samples of (a) whose block outputs the fixture keeps
+EDGE_TAP_ROWS = (0, 7)  # ... and of d, e, f and g
+
+
+def kmax(name):
+    return CONFIGS[name].get("kmax", KMAX)
+
+
+def tap_rows(name):
+    return EDGE_TAP_ROWS if name in EDGE_CONFIGS else TAP_ROWS
+
+
+def block_names(name):
+    """The top-level blocks of a configuration in call order, as build_plan names them."""
+    c = CONFIGS[name]
+    return (["encoder.down_sample_block"] + [f"encoder.block{i}" for i in range(c["blocks"])]
+            + [f"policy_head.block{i}" for i in range(c["heads"][0])] + [f"value_head.block{i}" for i in range(c["heads"][1])])
+
+
+def recorded_taps(name):
+    """The blocks whose outputs the fixture keeps: all of a and d; of e, f and g the last encoder block and the last block of each head
+    trunk (maps of at most 3x3, which separate a wrong encoder from a wrong head); none of b and c."""
+    c = CONFIGS[name]
+    if name in ("a", "d"):
+        return block_names(name)
+    if name not in EDGE_CONFIGS:
+        return []
+    return [f"encoder.block{c['blocks'] - 1}", f"policy_head.block{c['heads'][0] - 1}", f"value_head.block{c['heads'][1] - 1}"]
 
 
 def params(name):
@@ -67,26 +113,28 @@ def crc(a) -> int:
     return zlib.crc32(np.ascontiguousarray(a).tobytes())
 
 
-def draw_planes(name):
+def draw_planes(name, seed=None):
     c = CONFIGS[name]
-    return np.random.RandomState([c["seed"], 7777]).random_sample((c["n"], c["input_channels"], c["side"], c["side"])).astype(np.float32)
+    return np.random.RandomState([c["seed"] if seed is None else int(seed), 7777]).random_sample((c["n"], c["input_channels"], c["side"], c["side"])).astype(np.float32)
 
 
-def draw_valid_idx(name):
-    """Ascending valid sets, -1 padded: row 0 has one action, row 1 all KMAX, row 2 none."""
+def draw_valid_idx(name, seed=None):
+    """Ascending valid sets, -1 padded: row 0 has one action, row 1 all kmax, row 2 none; the others 2..kmax-1 (a, b, c) or 257..kmax-1
+    (the edge configurations: past one pass of 256 threads)."""
     c = CONFIGS[name]
-    A = c["side"] ** 2 * c["levels"]
-    rs = np.random.RandomState([c["seed"], 8888])
-    idx = np.full((c["n"], KMAX), -1, dtype=np.int32)
+    A, km = c["side"] ** 2 * c["levels"], kmax(name)
+    rs = np.random.RandomState([c["seed"] if seed is None else int(seed), 8888])
+    idx = np.full((c["n"], km), -1, dtype=np.int32)
     for r in range(c["n"]):
-        K = {0: 1, 1: KMAX, 2: 0}.get(r, int(rs.randint(2, KMAX)))
+        K = {0: 1, 1: km, 2: 0}.get(r, int(rs.randint(257 if name in EDGE_CONFIGS else 2, km)))
         idx[r, :K] = np.sort(rs.choice(A, size=K, replace=False))
     return idx
 
 
 @lru_cache(maxsize=None)
-def fixture():
-    return dict(np.load(FIXTURE))
+def fixture(name="a"):
+    """The arrays of the file that holds configuration `name`."""
+    return dict(np.load(EDGE_FIXTURE if name in EDGE_CONFIGS else FIXTURE))
 
 
 @lru_cache(maxsize=None)
@@ -95,22 +143,25 @@ def case(name):
     planes, valid_idx and the recorded outputs with d32 = max |ref32 - ref64| per output."""
     import torch
 
-    fx = fixture()
+    fx = fixture(name)
     names = json.loads(str(fx[f"{name}_keys"]))
     shapes = json.loads(str(fx[f"{name}_shapes"]))
-    sd = draw_state_dict(names, shapes, int(fx[f"{name}_seed"]))
+    seed = int(fx[f"{name}_seed"])
+    sd = draw_state_dict(names, shapes, seed)
     assert [crc(sd[k]) for k in names] == [int(v) for v in fx[f"{name}_crc"]], "the redrawn weights are not the recorded ones"
-    planes, idx = draw_planes(name), fx[f"{name}_valid_idx"]
-    assert crc(planes) == int(fx[f"{name}_planes_crc"])
+    planes, idx = draw_planes(name, seed), fx[f"{name}_valid_idx"]
+    assert crc(planes) == int(fx[f"{name}_planes_crc"]) and np.array_equal(idx, draw_valid_idx(name, seed))
     hp, md = params(name)
-    out = dict(name=name, hp=hp, md=md, cfg=CONFIGS[name], keys=names, state_dict={k: torch.from_numpy(v.copy()) for k, v in sd.items()},
+    out = dict(name=name, hp=hp, md=md, cfg=CONFIGS[name], kmax=kmax(name), seed=seed, keys=names, state_dict={k: torch.from_numpy(v.copy()) for k, v in sd.items()},
                planes=planes, valid_idx=idx)
     for k in ("prior32", "value32", "prior64", "value64"):
         out[k] = fx[f"{name}_{k}"]
     out["d32_prior"] = float(np.max(np.abs(out["prior32"] - out["prior64"])))
     out["d32_value"] = float(np.max(np.abs(out["value32"] - out["value64"])))
-    if name == "a":
-        out["tap_names"] = json.loads(str(fx["a_tap_names"]))
-        out["taps64"] = [fx[f"a_tap64_{i}"] for i in range(len(out["tap_names"]))]
-        out["tap_d32"] = [float(v) for v in fx["a_tap_d32"]]
+    out["tap_names"], out["taps64"], out["tap_d32"], out["tap_rows"] = [], [], [], tap_rows(name)
+    if f"{name}_tap_names" in fx:
+        out["tap_names"] = json.loads(str(fx[f"{name}_tap_names"]))
+        out["taps64"] = [fx[f"{name}_tap64_{i}"] for i in range(len(out["tap_names"]))]
+        out["tap_d32"] = [float(v) for v in fx[f"{name}_tap_d32"]]
+    assert out["tap_names"] == recorded_taps(name)
     return out

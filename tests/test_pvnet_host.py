@@ -1,11 +1,13 @@
 """
-Host side of the policy-value network (planning/mcts_zero/networks.py), against tests/golden/pvnet.npz recorded from the reference's
-PolicyValueNetwork (tests/golden/gen_pvnet_golden.py).  d32 = max |ref32 - ref64| per configuration and output is the reference's own
+Host side of the policy-value network (planning/mcts_zero/networks.py), against tests/golden/pvnet.npz and pvnet_edges.npz recorded from
+the reference's PolicyValueNetwork (tests/golden/gen_pvnet_golden.py).  d32 = max |ref32 - ref64| per configuration and output is the reference's own
 fp32 rounding distance, the unit of the bounds:
   * the restated module takes the reference's state_dict with strict=True and reproduces ref32 within 4 d32 (the same arithmetic in
     the same framework; the factor covers another conv algorithm);
-  * run_plan_numpy in fp64 on the folded plan reproduces ref64 and the block outputs of (a) to 1e-9 relative: folding is exact
+  * run_plan_numpy in fp64 on the folded plan reproduces ref64 and the recorded block outputs to 1e-9 relative: folding is exact
     algebra, and fp64 leaves that much room at these depths;
+  * the edges of the device kernels that d, e, f and g exist for are facts about their plans, asserted here from the kernels' own
+    tile constants, and the condition under which their seeds were kept holds on the fixture's own arrays;
   * shared weights are packed once and the op count is the one the block schedule implies;
   * every ValueError of the plan and of DevicePolicyValueNet fires before the device is touched.
 No GPU.
@@ -16,7 +18,7 @@ import torch
 
 from tests import pvnet_cases as pc
 
-NAMES = ("a", "b", "c")
+NAMES = ("a", "b", "c", "d", "e", "f", "g")
 
 
 def _module(case):
@@ -89,14 +91,19 @@ def test_plan_in_fp64_reproduces_ref64(name):
 def test_plan_taps_reproduce_the_block_outputs():
     from ipp_rl_amd.planning.mcts_zero.networks import build_plan, run_plan_numpy
 
-    case = pc.case("a")
-    plan, w = build_plan(case["hp"], case["md"], case["state_dict"], 20, dtype=np.float64)
-    rows = list(pc.TAP_ROWS)
-    assert [b for b, _ in plan.blocks] == case["tap_names"]
-    for name, want in zip(case["tap_names"], case["taps64"]):
-        _, _, tap = run_plan_numpy(plan, w, case["planes"][rows], case["valid_idx"][rows], dtype=np.float64, tap_op=plan.tap(name))
-        assert tap.shape == want.shape, name
-        assert np.abs(tap - want).max() <= 1e-9 * np.abs(want).max(), name
+    with_taps = [n for n in NAMES if pc.recorded_taps(n)]
+    assert with_taps == ["a", "d", "e", "f", "g"]
+    for cfg in with_taps:
+        case = pc.case(cfg)
+        plan, w = build_plan(case["hp"], case["md"], case["state_dict"], case["cfg"]["side"], dtype=np.float64)
+        rows = list(case["tap_rows"])
+        assert [b for b, _ in plan.blocks] == pc.block_names(cfg) and len(case["taps64"]) == len(case["tap_names"]) > 0
+        if cfg in ("a", "d"):
+            assert [b for b, _ in plan.blocks] == case["tap_names"]
+        for name, want in zip(case["tap_names"], case["taps64"]):
+            _, _, tap = run_plan_numpy(plan, w, case["planes"][rows], case["valid_idx"][rows], dtype=np.float64, tap_op=plan.tap(name))
+            assert tap.shape == want.shape, (cfg, name)
+            assert np.abs(tap - want).max() <= 1e-9 * np.abs(want).max(), (cfg, name)
 
 
 def _schedule(name):
@@ -128,7 +135,7 @@ def test_plan_packs_shared_weights_once(name):
     case = pc.case(name)
     plan, w = build_plan(case["hp"], case["md"], case["state_dict"], case["cfg"]["side"])
     n_ops, n_floats, kinds = _schedule(name)
-    assert len(plan.ops) == n_ops == {"a": 63, "b": 20, "c": 47}[name]
+    assert len(plan.ops) == n_ops == {"a": 63, "b": 20, "c": 47, "d": 30, "e": 34, "f": 25, "g": 13}[name]
     assert w.dtype == np.float32 and w.size == plan.n_floats == n_floats
     spans = sorted(plan.packed.values())
     assert spans[0][0] == 0 and all(a[0] + a[1] == b[0] for a, b in zip(spans, spans[1:])) and spans[-1][0] + spans[-1][1] == w.size
@@ -142,6 +149,75 @@ def test_plan_packs_shared_weights_once(name):
     assert not any(k.startswith("decoder") for k in plan.packed)
     if case["cfg"]["separable"]:
         assert not any(".residual_block_s" in k for k in plan.packed)
+
+
+def _kernel_constants():
+    """kBM, kBN, kBK, kThreads as csrc/k_pvnet.h states them."""
+    import os
+    import re
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    txt = open(os.path.join(root, "ipp-rl_amd", "csrc", "k_pvnet.h")).read()
+    line = re.search(r"constexpr int (kBM = \d+, kBN = \d+, kBK = \d+, kThreads = \d+);", txt).group(1)
+    return {k: int(v) for k, v in (item.split(" = ") for item in line.split(", "))}
+
+
+def test_edge_configurations_reach_their_edges():
+    """What d, e, f and g are for, as facts about their plans and the kernels' tile constants: a later change of kBM / kBN / kBK /
+    kThreads or of a configuration cannot silently un-cover an edge ("Policy-value network", lists them)."""
+    from ipp_rl_amd.planning.mcts_zero.networks import PV_CONV, PV_MIX, PV_POOL, build_plan
+
+    k = _kernel_constants()
+    kBN, kBK, T, mfma_n = k["kBN"], k["kBK"], k["kThreads"], 16
+    assert (k["kBM"], kBN, kBK, T) == (64, 64, 32, 256)
+    ops = {}
+    for name in pc.EDGE_NAMES:
+        case = pc.case(name)
+        plan, _ = build_plan(case["hp"], case["md"], case["state_dict"], case["cfg"]["side"])
+        ops[name] = plan.ops
+    convs = {n: [op for op in ops[n] if op["kind"] == PV_CONV] for n in ops}
+    pools = {n: [op for op in ops[n] if op["kind"] == PV_POOL] for n in ops}
+    mixes = {n: [op for op in ops[n] if op["kind"] == PV_MIX] for n in ops}
+    conv_k = {n: sorted({op["kh"] * op["kw"] * op["cin"] for op in convs[n]}) for n in ops}
+    for name in pc.EDGE_NAMES:  # more than one output-channel tile in every conv
+        assert all(op["cout"] > kBN for op in convs[name]), name
+    for name in ("d", "g"):  # the last tile ends inside a 16-column MFMA block
+        assert all(op["cout"] % mfma_n != 0 for op in convs[name]), name
+    assert [-(-op["cout"] // kBN) for op in convs["d"][:1] + convs["e"][:1] + convs["f"][:1] + convs["g"][:1]] == [2, 2, 5, 3]
+    # e, as shipped: no K tail in any conv between activations; its stem alone (7 x 7 x 16 planes = 784 = 24.5 chunks) has one
+    stem_k = 49 * pc.CONFIGS["e"]["input_channels"]
+    assert convs["e"][0]["src"] == -1 and conv_k["e"] == sorted({stem_k, 128, 384, 1152}) and all(K % kBK == 0 for K in conv_k["e"] if K != stem_k)
+    assert not any(K % kBK == 0 for K in conv_k["d"]) and {648, 216, 72} <= set(conv_k["d"])
+    # pool_channels: the g0 loop twice (f), one slice with idle threads (g), pixel slices with idle threads (d's mix: T // 24 = 10, 16 idle)
+    assert any(op["cin"] >= T for op in pools["f"]) and all(T // 2 < op["cin"] < T for op in pools["g"])
+    assert any(op["cout"] - op["cin"] > T for op in mixes["f"])  # the context loop of k_pv_mix twice
+    assert all(op["cin"] == 24 and T % op["cin"] != 0 for op in mixes["d"]) and mixes["d"] and not mixes["g"]
+    # the head pools average more than one pixel, against the reference
+    assert all(op["hin"] * op["win"] == 9 for op in pools["d"]) and all(op["hin"] * op["win"] == 4 for op in pools["e"] + pools["g"])
+    for name in pc.EDGE_NAMES:  # a second pass of the policy head's loops over the slots
+        K = (pc.case(name)["valid_idx"] >= 0).sum(axis=1)
+        assert pc.case(name)["kmax"] == 300 > T and K[0] == 1 and K[1] == 300 and K[2] == 0 and np.all(K[3:] > T), name
+    # the value head's dot product over 2 C pooled values takes a second pass in f and g; f's value head is clamped by its ReLU on
+    # every row (value = softplus(0)^2 + 2 softplus(0)), so of the two only g's value says anything about that pass
+    dead = np.log(2.0) ** 2 + 2 * np.log(2.0)
+    assert np.all(pc.case("f")["value64"] == dead) and (pc.case("g")["value64"] != dead).sum() >= 4
+    assert 2 * pc.CONFIGS["g"]["channels"] > T
+
+
+@pytest.mark.parametrize("name", pc.EDGE_NAMES)
+def test_edge_seeds_give_the_room_of_the_first_cases(name):
+    """The condition under which the generator kept a seed, from the fixture's own arrays: d32 > 0, and the float32 NumPy run of the
+    plan (another fp32 summation order, on the CPU) within 2 d32 of ref64 on prior and value."""
+    from ipp_rl_amd.planning.mcts_zero.networks import build_plan, run_plan_numpy
+
+    case = pc.case(name)
+    assert case["d32_prior"] > 0 and case["d32_value"] > 0 and all(d > 0 for d in case["tap_d32"])
+    assert case["seed"] >= case["cfg"]["seed"]
+    plan, w = build_plan(case["hp"], case["md"], case["state_dict"], case["cfg"]["side"])
+    prior, value = run_plan_numpy(plan, w, case["planes"], case["valid_idx"], dtype=np.float32)
+    r_p, r_v = np.abs(prior - case["prior64"]).max() / case["d32_prior"], np.abs(value - case["value64"]).max() / case["d32_value"]
+    print(f"{name}: seed {case['seed']}: float32 NumPy plan vs ref64: prior {r_p:.2f} d32, value {r_v:.2f} d32")
+    assert r_p <= 2 and r_v <= 2
 
 
 def test_folding_uses_each_batchnorms_own_eps():

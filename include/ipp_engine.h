@@ -817,6 +817,9 @@ typedef struct ipp_selfplay {
  * for a temperature-0 step, the one-hot arg-max of policy_1's row (ipp_mcts_policy at temperature 1: the forced-playout-pruned visits over
  * their sum; ties by an IPP_SP_ARGMAX_STREAM draw); the action index is the inverse CDF of that policy in ascending action order at an
  * IPP_SP_ACTION_STREAM uniform (:135) and action[e] its waypoint (:136).  valid_idx [dev] [B][kmax] (ipp_mcts_policy's), ok [dev] [B].
+ * A row with ok[e] == 1 that has no mass to draw from (an empty valid set, a NaN, a maximum or a sum that is not positive and finite, or
+ * the drawn valid index outside [0, num_actions)) is treated like ok[e] == 0; in both cases the ring row keeps its earlier policy and
+ * valid set and its flag becomes 0.
  */
 int ipp_selfplay_record(const ipp_selfplay* sp, int64_t step, const double* policy_t, const double* policy_1, const int32_t* valid_idx,
                         const int32_t* ok, void* stream);

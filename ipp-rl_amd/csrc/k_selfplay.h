@@ -30,6 +30,17 @@ __device__ __forceinline__ double sp_uniform(uint64_t q, uint64_t subseq, uint64
 // counter of the per-step draws of an env: (global env id, depth in the episode); the episode is the subsequence offset
 __device__ __forceinline__ uint64_t sp_step_counter(long long gid, int depth) { return ((uint64_t)gid << 20) + (uint64_t)depth; }
 
+// an env's step without a sample (no policy, or none with mass): a zero budget ends the episode inside the step launch (a reset exactly
+// like a budget end), the action is the current waypoint (no cost).  The row's planes were overwritten for this step: it is no longer
+// a committed sample; its earlier policy and valid set stay as they were.
+__device__ __forceinline__ void sp_end_without_sample(const ipp_selfplay& sp, int e, size_t row) {
+    sp.forced[e] = 1;
+    sp.budget[e] = 0.0;
+    for (int c = 0; c < 3; ++c) sp.action[3 * e + c] = sp.prev[3 * e + c];
+    sp.action_idx[e] = -1;
+    sp.r_flags[row] = 0;
+}
+
 __global__ __launch_bounds__(64) void k_sp_record(ipp_selfplay sp, long long step, const double* __restrict__ pol_t,
                                                   const double* __restrict__ pol_1, const int32_t* __restrict__ vidx,
                                                   const int32_t* __restrict__ ok) {
@@ -41,16 +52,8 @@ __global__ __launch_bounds__(64) void k_sp_record(ipp_selfplay sp, long long ste
     const int e = blockIdx.x, lane = threadIdx.x;
     if (e >= sp.num_envs) return;
     const size_t row = (size_t)(step % sp.slots) * sp.num_envs + e;
-    if (!ok[e]) {
-        // no policy: no sample; a zero budget ends the episode inside the step launch (a reset exactly like a budget end), the action
-        // is the current waypoint (no cost).  The row's planes were overwritten for this step: it is no longer a committed sample.
-        if (lane == 0) {
-            sp.forced[e] = 1;
-            sp.budget[e] = 0.0;
-            for (int c = 0; c < 3; ++c) sp.action[3 * e + c] = sp.prev[3 * e + c];
-            sp.action_idx[e] = -1;
-            sp.r_flags[row] = 0;
-        }
+    if (!ok[e]) {  // no policy: no sample
+        if (lane == 0) sp_end_without_sample(sp, e, row);
         return;
     }
     const int depth = sp.depth[e];
@@ -59,16 +62,24 @@ __global__ __launch_bounds__(64) void k_sp_record(ipp_selfplay sp, long long ste
     const double* src = (t0 ? pol_1 : pol_t) + (size_t)e * kmax;
     const int32_t* vi = vidx + (size_t)e * kmax;
     double vmax = -INFINITY;
+    bool has_nan = false;
     for (int k = lane; k < kmax; k += 64) {
         const int32_t a = vi[k];
         const double p = a >= 0 ? src[k] : 0.0;
         s_p[k] = p;
         s_i[k] = a;
         if (a >= 0) vmax = fmax(vmax, p);
+        has_nan |= p != p;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) vmax = fmax(vmax, __shfl_xor(vmax, o, 64));
     __syncthreads();
+    // ok[] promises a policy with mass on the valid set.  One that has none (an empty valid set, all zeros, a NaN, an infinity) is no
+    // sample: np.random.choice raises on it; here the env ends like a root without a policy
+    if (__any(has_nan) || !(vmax > 0.0) || vmax == INFINITY) {
+        if (lane == 0) sp_end_without_sample(sp, e, row);
+        return;
+    }
     if (t0) {
         // np.random.choice among the most visited actions (ascending action order), from a counter-based uniform
         int n_ties = 0, best = -1;
@@ -94,11 +105,7 @@ __global__ __launch_bounds__(64) void k_sp_record(ipp_selfplay sp, long long ste
         for (int k = lane; k < kmax; k += 64) s_p[k] = (k == best) ? 1.0 : 0.0;
         __syncthreads();
     }
-    // the sparse sample: fp32 probabilities and the valid indices on the row's kmax slots
-    for (int k = lane; k < kmax; k += 64) {
-        sp.r_policy[row * kmax + k] = (float)s_p[k];
-        sp.r_idx[row * kmax + k] = s_i[k];
-    }
+    int a = -1;
     if (lane == 0) {
         // inverse CDF in ascending action order: cdf = cumsum(p) / sum(p), the first k with cdf[k] > u (NumPy's sequential cumsum; the
         // actions outside the valid set have p = 0 and leave every partial sum as it is)
@@ -115,15 +122,20 @@ __global__ __launch_bounds__(64) void k_sp_record(ipp_selfplay sp, long long ste
             if (c / tot > u) { pick = k; break; }
         }
         if (pick < 0) pick = last;  // (cdf[-1] / cdf[-1] == 1 > u: not reached)
-        const int a = s_i[pick];
-        if (a < 0 || a >= sp.num_actions) {  // (no mass on the valid set: ok[] promises otherwise; ended like a root without a policy)
-            sp.forced[e] = 1;
-            sp.budget[e] = 0.0;
-            for (int c = 0; c < 3; ++c) sp.action[3 * e + c] = sp.prev[3 * e + c];
-            sp.action_idx[e] = -1;
-            sp.r_flags[row] = 0;
-            return;
-        }
+        a = s_i[pick];
+        if (!(tot > 0.0) || !(tot < INFINITY) || a >= sp.num_actions) a = -1;  // (a sum without mass; a valid index that is no action)
+    }
+    a = __shfl(a, 0, 64);
+    if (a < 0) {
+        if (lane == 0) sp_end_without_sample(sp, e, row);
+        return;
+    }
+    // the sparse sample: fp32 probabilities and the valid indices on the row's kmax slots
+    for (int k = lane; k < kmax; k += 64) {
+        sp.r_policy[row * kmax + k] = (float)s_p[k];
+        sp.r_idx[row * kmax + k] = s_i[k];
+    }
+    if (lane == 0) {
         sp.action_idx[e] = a;
         for (int q = 0; q < 3; ++q) sp.action[3 * e + q] = sp.actions[3 * (size_t)a + q];
         sp.r_flags[row] = kSpPending;

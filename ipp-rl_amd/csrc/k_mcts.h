@@ -209,7 +209,11 @@ __global__ __launch_bounds__(256) void k_mcts_select(ipp_mcts_tables m, const in
                     if (nsa < nfp) uct = INFINITY;
                 }
                 const double u = m.tie_break ? mc_u01(mc_mix(seed ^ mc_mix(((uint64_t)(uint32_t)(cur + m.root_base * m.nodes_per_root) << 32) | (uint32_t)(k + 1)) ^ ((uint64_t)(sim0 + w) << 20))) : 0.0;
-                if (uct > best || (uct == best && (m.tie_break ? u > best_u : k < best_k))) { best = uct; best_k = k; best_u = u; best_nsa = nsa; best_a = ai; best_c = ci; }
+                // (selects, not a branch around the six assignments: in the NE = 0 loop the compiler's code for the branch kept the
+                // OLD best_k on a lane whose later edge tied the score and won on the draw, next to that edge's action, count and child)
+                const bool take = uct > best || (uct == best && (m.tie_break ? u > best_u : k < best_k));
+                best = take ? uct : best; best_k = take ? k : best_k; best_u = take ? u : best_u;
+                best_nsa = take ? nsa : best_nsa; best_a = take ? ai : best_a; best_c = take ? ci : best_c;
             };
             if (NE > 0) {
 #pragma unroll

@@ -146,10 +146,8 @@ struct View {
     int plw;         // the prior table of the patch kernel is P0(|drow| < plw, |dcol| < plw)
     int pcap;        // column records per item kept in LDS (the rest in the item's global scratch block)
     int punits;      // most (64 lanes x 2 cells) units of one patch
-    // split step (k_step_split.h): the items' blocks, written by the prologue kernel and read by the unit kernel
-    float* blk;      // [max_batch][blk_stride], indexed by blk_pos0 + the workgroup index of the prologue launch (= dispatch position)
-    int blk_stride;  // floats per block (SplitBlk::floats)
-    int blk_pos0;    // first block of this launch (ipp_step_parts: the part's first position)
+    int pos0;        // dispatch position of this launch's first item (ipp_step_parts: the part's first position; else 0): the budget
+                     // ledger's refill list is indexed by pos0 + the workgroup index
     // kCountSlots slots of 16 words (128 B apart): a workgroup adds its totals to slot (item % kCountSlots), word 0 =
     // streamed floats (SURVEY 8(d) count), word 8 = floats re-read for the mask.  One address for all workgroups cost
     // 5 % (one counter) / 19 % (two) of the fused step kernel: the waves' exits queued up behind same-address atomics.

@@ -18,7 +18,6 @@
 #include "k_gain_factor.h"
 #include "k_step_factor.h"
 #include "k_step_patch.h"
-#include "k_step_split.h"
 #include "k_gain_wave.h"
 #include "k_misc.h"
 #include "k_grf_dft.h"
@@ -127,7 +126,7 @@ struct Layout {
     int N, Npad, T, n_tiles, win_tiles, MC, FC, QS, q_rows, VEC;
     bool patch;
     PatchGeo pg;
-    uint64_t off_mean, off_diag, off_gt, off_gtslot, off_prior, off_rank, off_span, off_cnt, off_icnt, off_cov, off_blk, off_hdr, off_linv, off_yv, off_q, off_wc,
+    uint64_t off_mean, off_diag, off_gt, off_gtslot, off_prior, off_rank, off_span, off_cnt, off_icnt, off_cov, off_hdr, off_linv, off_yv, off_q, off_wc,
         off_partial, off_dbg, off_grfh, off_grfcs, off_grfg, off_grfhp, off_grfamp, off_grfraw, off_grfraw2, off_sc_hdr, off_sc_ext, off_sc_mask, off_sc_G, off_sc_P, off_tr_cov, off_tr_diag, off_tr_meta, off_sc_ndiag, total, cov_slot_floats;
 };
 
@@ -257,7 +256,7 @@ int plan(const ipp_config& c, int kind, const Switches& sw, Layout& L, bool allo
         // (Since the rectangle metadata the fused kernel is ahead up to 16384 envs of 50x50 -- 8192: 24.7 vs 23.4 M, 16384:
         // 26.0 vs 23.7 M env-steps/s -- and the split path from 32768: 28.3 vs 26.9 M; on 100x100 the split path stays 23 % ahead.)
         if (c.tile_threads <= 0 && c.node_capacity <= 0 && c.capacity >= ((int64_t)c.x_dim * c.y_dim >= 6000 ? 8192 : 24576)) L.T = 128;
-        if (L.patch) L.T = 64 * sw.patch_waves;  // one fused kernel for every batch size
+        if (L.patch) L.T = 64 * kPatchWavesDefault;  // one fused kernel for every batch size
         if (L.T > 512) return fail(-1, "tile_threads must be <= 512 for IPP_FACTOR");
         L.n_tiles = (n4 + 63) / 64;
         L.Npad = L.n_tiles * 64 * L.VEC;
@@ -283,7 +282,6 @@ int plan(const ipp_config& c, int kind, const Switches& sw, Layout& L, bool allo
     L.off_cnt = o; o += up((uint64_t)kCountSlots * 128);
     L.off_icnt = o; o += up((uint64_t)c.max_batch * 16);
     L.off_cov = o; o += up(cap * L.cov_slot_floats * 4);
-    L.off_blk = o; o += L.patch ? up(mb * SplitBlk::floats(L.pg.plw, c.rank_cap) * 4) : 0;  // item blocks of the split step (k_step_split.h)
     L.off_hdr = o; o += up(mb * sizeof(ItemHdr));
     L.off_linv = o; o += up(mb * L.MC * L.MC * 4);
     L.off_yv = o; o += up(mb * L.MC * 4);
@@ -406,7 +404,7 @@ void timed_launch(Engine* e, int kind, void (*kernel)(P...), dim3 grid, dim3 blo
 
 void prof_drain(Engine* e) {
     // per kind: sum of the dispatches' durations + the union of their [start, stop] intervals (launches of different streams
-    // overlap); slot 3: the union over EVERY launch (a split step is a prologue launch and a unit launch: both are the step)
+    // overlap); slot 3: the union over EVERY launch (a two-kernel step is a prologue launch and a gain launch: both are the step)
     auto& pend = e->prof_pending;
     if (pend.empty()) return;
     std::vector<std::pair<float, float>> iv[kProfKinds];  // ms behind the first start of this batch
@@ -451,27 +449,22 @@ size_t gain_lds_bytes(const View& v, int q_chunk, int lut_cap) {
     return (b + 15) & ~(size_t)15;
 }
 
-// The instantiations of k_step_patch -- X(NW, KPN, MINW, SPLIT, RJN, an IPP_BUDGET form exists) -- and of k_tree_patch -- X(NW, RJN):
-// the launches and the LDS opt-in of engine creation both go through these lists.
-#define IPP_STEP_PATCH_KERNELS(X)                    \
-    X(1, kPatchKP, kPatchMinW, false, 0, false)      \
-    X(2, kPatchKP, kPatchMinW, false, 0, true)       \
-    X(3, kPatchKP, kPatchMinW, false, 0, true)       \
-    X(3, kPatchKP, kPatchMinW, false, 1, true)       \
-    X(3, kPatchKP, kPatchMinW, false, 2, true)       \
-    X(4, kPatchKP, kPatchMinW, false, 0, false)      \
-    X(2, IPP_PATCH_BIGKP, 6, false, 0, true)         \
-    X(1, kPatchKP, kSplitMinWP, true, 0, false)      \
-    X(2, kPatchKP, kSplitMinWP, true, 0, false)      \
-    X(3, kPatchKP, kSplitMinWP, true, 0, false)
-#define IPP_TREE_PATCH_KERNELS(X) X(2, 0) X(3, 0) X(3, 1) X(4, 0)
+// The instantiations of k_step_patch -- X(NW, KPN, MINW, RJN), each in its plain and its IPP_BUDGET form -- and of k_tree_patch --
+// X(NW, RJN): the launches and the LDS opt-in of engine creation both go through these lists.
+#define IPP_STEP_PATCH_KERNELS(X)      \
+    X(2, kPatchKP, kPatchMinW, 0)      \
+    X(3, kPatchKP, kPatchMinW, 0)      \
+    X(3, kPatchKP, kPatchMinW, 1)      \
+    X(3, kPatchKP, kPatchMinW, 2)      \
+    X(2, IPP_PATCH_BIGKP, 6, 0)
+#define IPP_TREE_PATCH_KERNELS(X) X(3, 0) X(3, 1)
 
-using StepPatchKernel = decltype(&k_step_patch<1>);
-using TreePatchKernel = decltype(&k_tree_patch<2>);
+using StepPatchKernel = decltype(&k_step_patch<3>);
+using TreePatchKernel = decltype(&k_tree_patch<3>);
 template <bool BUD>
 StepPatchKernel patch_kernel(const PatchVariant& pv) {  // nullptr: not instantiated
-#define X(NW, KPN, MINW, SPLIT, RJN, HASBUD) \
-    if ((HASBUD || !BUD) && pv.waves == NW && pv.kpn == KPN && pv.minw == MINW && pv.split == SPLIT && pv.rjn == RJN) return k_step_patch<NW, KPN, MINW, SPLIT, RJN, BUD && HASBUD>;
+#define X(NW, KPN, MINW, RJN) \
+    if (pv.waves == NW && pv.kpn == KPN && pv.minw == MINW && pv.rjn == RJN) return k_step_patch<NW, KPN, MINW, RJN, BUD>;
     IPP_STEP_PATCH_KERNELS(X)
 #undef X
     return nullptr;
@@ -491,15 +484,12 @@ void launch_chunk(Engine* e, const View& v, const int32_t* env_ids, const int32_
                   hipEvent_t prep_done, const AutoReset& ar) {
     if (e->patch) {  // compact column patches: one fused kernel, one small workgroup per item (k_step_patch.h)
         if constexpr (MC == 9 && VEC == 2) {
-            // (the budget ledger: the IPP_BUDGET instantiation of the kernel the launch would run otherwise -- budget_launch_error has
-            // refused the split step and the one- / four-wave A/B engines)
+            // (the budget ledger: the IPP_BUDGET instantiation of the kernel the launch would run otherwise)
             const PatchVariant& pv = pick(e->pp, n);
             View vp = v;
             vp.pcap = pv.pcap;
-            timed_launch(e, pv.split ? 2 : 0, (flags & IPP_BUDGET) ? patch_kernel<true>(pv) : patch_kernel<false>(pv), dim3(n), dim3(64 * pv.waves), pv.lds, s, vp,
+            timed_launch(e, 0, (flags & IPP_BUDGET) ? patch_kernel<true>(pv) : patch_kernel<false>(pv), dim3(n), dim3(64 * pv.waves), pv.lds, s, vp,
                          env_ids, n, action, prev, noise, flags, status, reward, ar);
-            // split step (k_step_split.h): item-parallel prologue kernel, then one wave per (item, unit)
-            if (pv.split) timed_launch(e, 0, k_step_units<>, dim3(split_grid(n, v.punits)), dim3(64), e->pp.lds_u, s, v, n, flags, reward, ar);
         }
         if (prep_done) (void)hipEventRecord(prep_done, s);
         return;
@@ -835,22 +825,17 @@ int ipp_engine_create_prior(const ipp_config* cfg, int32_t kind, int device, voi
     if (v.rect_meta) { e->rect_commit = e->rect_ok; e->rect_tree = true; }
     v.patch = L.patch ? 1 : 0;
     v.pw = v.ph = v.pstride = v.plw = v.pcap = v.punits = 0;
-    v.blk = nullptr; v.blk_stride = 0; v.blk_pos0 = 0;
+    v.pos0 = 0;
     e->patch = L.patch;
     if (L.patch) {
         v.clip_cols = 1;
         v.rect_meta = 1;
         v.pw = L.pg.pw; v.ph = L.pg.ph; v.pstride = L.pg.pstride; v.plw = L.pg.plw; v.punits = L.pg.punits;
-        v.blk = reinterpret_cast<float*>(base + L.off_blk);
-        v.blk_stride = (int)SplitBlk::floats(v.plw, cfg->rank_cap);
         e->pp = make_patch_plan(v, sw);
         v.pcap = e->pp.tier[0].pcap;
-        // every variant of the plan is an instantiated kernel; where its IPP_BUDGET form is one too, budget steps may run it
-        bool have = patch_kernel<false>(e->pp.split) && tree_patch_kernel(e->pp.tree);
-        for (int i = 0; i < e->pp.n_tiers; ++i) {
-            have = have && patch_kernel<false>(e->pp.tier[i]);
-            e->pp.tier[i].budget = patch_kernel<true>(e->pp.tier[i]) != nullptr;
-        }
+        // every variant of the plan is an instantiated kernel, in its plain and its IPP_BUDGET form
+        bool have = tree_patch_kernel(e->pp.tree) != nullptr;
+        for (int i = 0; i < e->pp.n_tiers; ++i) have = have && patch_kernel<false>(e->pp.tier[i]) && patch_kernel<true>(e->pp.tier[i]);
         if (!have) { delete e; return fail(-3, "the patch launch plan names a kernel that is not instantiated"); }
     }
     v.win_tiles = L.win_tiles;
@@ -938,8 +923,8 @@ int ipp_engine_create_prior(const ipp_config* cfg, int32_t kind, int device, voi
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_prepare<25, IPP_DENSE>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     {  // patch kernels: opt in to more than the default 64 KB of dynamic LDS
         auto opt_in = [](auto* kernel) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); };
-        // (the plain form and the IPP_BUDGET form; where there is none, BUD = HASBUD = false names the plain form again)
-#define X(NW, KPN, MINW, SPLIT, RJN, HASBUD) opt_in(k_step_patch<NW, KPN, MINW, SPLIT, RJN, false>); opt_in(k_step_patch<NW, KPN, MINW, SPLIT, RJN, HASBUD>);
+        // (the plain form and the IPP_BUDGET form)
+#define X(NW, KPN, MINW, RJN) opt_in(k_step_patch<NW, KPN, MINW, RJN, false>); opt_in(k_step_patch<NW, KPN, MINW, RJN, true>);
         IPP_STEP_PATCH_KERNELS(X)
 #undef X
 #define X(NW, RJN) opt_in(k_tree_patch<NW, RJN>);
@@ -1096,7 +1081,7 @@ int ipp_engine_info(void* engine, ipp_info* out) {
     out->patch_waves = e->patch ? e->pp.tier[0].waves : 0;
     out->patch_big_min_items = e->patch ? e->pp.tier[e->pp.big_tier].min_items : 0;  // (tier[0].min_items = 0: no such tier)
     out->patch_two_wave_min_items = e->patch ? e->pp.tier[e->pp.two_wave_tier].min_items : 0;
-    out->patch_split_min_items = e->patch ? e->pp.split.min_items : 0;
+    out->patch_split_min_items = 0;  // (always: the field only keeps the struct's layout)
     return 0;
 }
 
@@ -1188,8 +1173,6 @@ static const char* budget_launch_error(const Engine* e, uint32_t flags, int n, c
     if (flags & IPP_PREDICT_ONLY) return "IPP_BUDGET: not with IPP_PREDICT_ONLY (the ledger charges committed steps)";
     if (env_ids) return "IPP_BUDGET: full-batch in-place steps only (env_ids == NULL)";
     if (n > e->v.cap) return "IPP_BUDGET: more items than env slots";
-    if (pick(e->pp, n).split) return "IPP_BUDGET: not on the split step (IPP_SPLIT)";
-    if (!pick(e->pp, n).budget) return "IPP_BUDGET: engines of two or three waves per item only (IPP_PATCH_WAVES)";
     if (e->step_chunks > 1) return "IPP_BUDGET: not with a chunked step (IPP_STEP_CHUNKS)";
     if (flags & IPP_RESET_ON_DONE) {
         if (reset_src || reset_gt) return "IPP_RESET_ON_DONE: the resets come from the ledger (reset_src and reset_gt must be NULL)";
@@ -1266,7 +1249,7 @@ int ipp_step_parts(void* engine, int32_t n, const double* action, double* prev_a
     e->last_n = n;
     for (int p = 0; p < n_parts; ++p) {
         View v = e->v;  // (the per-item arrays keep their batch indexing: a part is a range of positions of the order)
-        v.blk_pos0 = part_begin[p];  // (the split step's item blocks are indexed by the dispatch position)
+        v.pos0 = part_begin[p];  // (the budget ledger's refill list is indexed by the dispatch position)
         v.item_order = e->v.item_order + part_begin[p];
         v.item_order_n = part_begin[p + 1] - part_begin[p];
         launch_chunk<9, 2>(e, v, nullptr, nullptr, v.item_order_n, action, prev_action, meas_noise, flags, reward, status,

@@ -1,18 +1,17 @@
-// The unit body of the patch kernels -- ONE body for the fused env step (k_step_patch.h), the tree-search predict step
-// (k_tree_patch.h) and the unit-parallel kernel of the split env step (k_step_split.h): Wc = (P[:,F] H_F^T) L^-1 on the cells of the new
-// patch, the masked trace reduction, and the writes of the step.
+// The unit body of the patch kernels -- ONE body for the fused env step (k_step_patch.h) and the tree-search predict step
+// (k_tree_patch.h): Wc = (P[:,F] H_F^T) L^-1 on the cells of the new patch, the masked trace reduction, and the writes of the step.
 // mapping/mappings.py:185-197 (Wc, P' = P - Wc Wc^T, x' = x + Wc L^-T v), planning/common/rewards.py:8-31 (mask, reward).
 //
 // What differs between the kernels sits behind the `Io` policy: where the pre-step mean / variance of a cell come from, how a stored
 // row is addressed (one buffer resource per item + scalar offset, or a 64-bit offset from View::cov), where a column record's -HT
-// values are read (the workgroup's LDS staging or the item's global block) and where the results go.
+// values are read (the workgroup's LDS staging) and where the results go.
 //
 //   * A UNIT is 64 lanes x 2 consecutive cells of the new rectangle enumerated row-major over ITS OWN width wn (index -> (prow, pcol)
 //     through a per-item reciprocal), not over the fixed patch stride pw: 3.8 units per item at the headline instead of 4.6.  The
 //     address of a cell in a (shifted) stored patch is still prow * pw + pcol.
 //   * The records that meet a unit's rows are a 64-bit mask per page of 64 records (their rectangles sit in the lanes of two registers:
 //     two compares and a ballot), walked with s_ff1 / s_bitset0 -- the record index of a row is born in an SGPR.  Order of
-//     accumulation: increasing record index, whatever kernel runs the unit: results are bit-identical between the three.
+//     accumulation: increasing record index, whatever kernel runs the unit: results are bit-identical between the two.
 //   * Request groups of KP rows (all KP requests leave before the first wait); the remainder of a page in a group of 2, 4 or KP rows
 //     whose surplus rows repeat the group's first record with the request masked off.  A row's -HT values live in the lanes of ONE
 //     register (value l & 15 in lane l) and reach the 18 FMAs through v_fmac_f32_dpp row_newbcast.
@@ -67,9 +66,9 @@ struct UnitArgs {
     int item;           // (timing builds: the per-unit trace)
 };
 
-// LDS tables a unit reads (the fused kernels carve them out of PatchLds, the split kernel out of its own small block).
+// LDS tables a unit reads (carved out of PatchLds).
 struct UnitLds {
-    const float* rec;    // column records staged in LDS ([cap][kPatchRec]; Io::coef decides whether they are read from here)
+    const float* rec;    // column records staged in LDS ([cap][kPatchRec]; read through Io::coef)
     const float* Ls;     // L^-1 [9][9]
     const float* ys;     // y [9]
     const float* lut;    // P0(|drow|, |dcol|), plw x plw
@@ -195,7 +194,7 @@ __device__ __forceinline__ void patch_unit(const View& v, const UnitLds& ul, Io&
         }
     };
     // FAST: records of one register page, taken off its mask in increasing order -- index, patch offset and rectangle are scalars
-    // (s_ff1 / v_readlane with a scalar lane select), -HT through the Io policy (LDS record or the item's global block)
+    // (s_ff1 / v_readlane with a scalar lane select), -HT through the Io policy (the LDS record)
     auto fast_group = [&](unsigned long long& mk, int page, int nreal, auto n_tag, auto full_tag) {
         constexpr bool FULL = decltype(full_tag)::value;
         constexpr int N = decltype(n_tag)::value;
@@ -272,7 +271,7 @@ __device__ __forceinline__ void patch_unit(const View& v, const UnitLds& ul, Io&
     // to scratch, per unit and wave; the L^-1 FMAs below cover the round trip)
     float md_in[2][VEC];
     io.load_pre(cell0, flat, rrow, rcol, md_in);
-    // ---- wait (first unit of a wave in the fused kernels only) for L^-1 and y, then Wc = (P[:,F] H_F^T) L^-1 in place (column j
+    // ---- wait (first unit of a wave only) for L^-1 and y, then Wc = (P[:,F] H_F^T) L^-1 in place (column j
     // needs the entries b <= j)
     if (!solved && ua.solve_flag) {
         while (__hip_atomic_load(ua.solve_flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) __builtin_amdgcn_s_sleep(4);

@@ -10,7 +10,7 @@
 // of that column (lanes outside the column's rectangle masked), whatever the grid width, and a column slot is 2.6 KB instead
 // of Npad floats.  The appended columns are written the same way: m coalesced row writes per unit.
 //
-// k_step_patch<NW, KP, MINW, SPLIT = false>: the FUSED step, one workgroup of NW waves per item (default 3 waves at MINW = 6 waves per
+// k_step_patch<NW, KP, MINW>: the FUSED step, one workgroup of NW = 2 or 3 waves per item (default 3 waves at MINW = 6 waves per
 // SIMD: 80 VGPRs, 8 workgroups = 2048 item slots per CU x 256).  Per item:
 //   prologue   inputs + the rectangles of all stored columns in one batch of loads; wave 0 evaluates the fp64 header and hands it over
 //              through LDS; the CONTRIBUTING columns (rectangle meets the footprint: the others have an exactly zero row of H U^T)
@@ -20,11 +20,8 @@
 //              P0(|drow| < plw, |dcol| < plw) is built under the gather's round trip
 //   algebra    wave 0: S, Cholesky, L^-1, y in registers (solve_wave_fast, fp64); wave 1: the observation (observe_wave); the other
 //              wave(s) stream from the start
-//   units      k_patch_units.h (shared with k_tree_patch and the split step), drawn from an LDS ticket
+//   units      k_patch_units.h (shared with k_tree_patch), drawn from an LDS ticket
 //   results    last wave: reward = sum of the units' reductions IN UNIT ORDER / (cost + 1), rank, rectangles, the scheduled reset
-// k_step_patch<NW, KP, MINW, SPLIT = true>: the PROLOGUE KERNEL of the split step (k_step_split.h): the same code up to the m x m
-// algebra; instead of running the units it leaves header, tables, L^-1 | y and the records in the item's block of
-// View::blk for the unit-parallel kernel k_step_units.
 // Arithmetic per cell (prior term, order of the stored rows, L^-1 in the epilogue, reward sums in unit order) is the one of
 // gain_tiles<PRE, RECT> (k_gain_factor.h); the m x m algebra and the observation are the shared device functions of k_prepare.h.
 // mapping/mappings.py:178-197, planning/common/rewards.py:8-31.
@@ -94,22 +91,6 @@ struct PatchLds {
     }
 };
 
-// The item's BLOCK of the split step (View::blk, one per dispatch position of a launch; k_step_split.h): written by the prologue
-// kernel (k_step_patch<1, ., ., true>), read by the unit-parallel kernel.  Offsets in floats from the block's start; every part
-// starts on a 128-byte line.
-struct SplitBlk {
-    static constexpr int kHdr = 0;      // 32 ints: the words below
-    static constexpr int kSync = 32;    // 64 words = 32 x 8 bytes: [0] arrival counter of the units, [1 + u] reduction of unit u (fp64; <= 31 units)
-    static constexpr int kTab = 96;     // fb_yx [36] | fb_w [36] | L^-1 [81] y [9] pad [6] | prior table [lutf4]: copied to LDS by every unit
-    static constexpr int kTabFixed = 72 + PatchLds::LQ;
-    // header words
-    enum { ITEM = 0, ENV, M, NC, NUNITS, RANK, BITS, RECT, TSPAN, RESET, COST_LO, COST_HI, HDR_WORDS };
-    enum { B_RF1 = 1, B_COMMIT = 2, B_DEAD = 4 };
-    __host__ __device__ static int lutf4(int plw) { return (plw * plw + 3) & ~3; }
-    __host__ __device__ static int rec_off(int plw) { return (kTab + kTabFixed + lutf4(plw) + 31) & ~31; }
-    __host__ __device__ static size_t floats(int plw, int rank_cap) { return ((size_t)rec_off(plw) + (size_t)rank_cap * kPatchRec + 31) & ~(size_t)31; }
-};
-
 }  // namespace ipp
 #include "k_patch_units.h"
 namespace ipp {
@@ -124,7 +105,6 @@ struct StepIo {
     float* mean_rw;
     float* diag_rw;
     bool cov_only;
-    bool wt_planes;  // mean / variance stores write-through (split step, envs reset by the launch)
     int m, row0_bytes, pstride_bytes;
     __device__ __forceinline__ rowv row_load(unsigned cofs, unsigned voff) const {
         // one resource for the whole item, the patch offset as the request's scalar offset (a resource per row was four
@@ -143,17 +123,8 @@ struct StepIo {
             float od[2], om[2];
 #pragma unroll
             for (int c = 0; c < 2; ++c) { od[c] = md[1][c] - dred[c]; om[c] = md[0][c] + dmean[c]; }
-            if (!wt_planes) {
-                store_vec<2>(diag_rw + cell0, od);
-                if (!cov_only) store_vec<2>(mean_rw + cell0, om);
-            } else {
-                // split step, an env that this launch resets: 8-byte agent-scope stores = write-through (sc1), in memory before this
-                // wave's arrival whatever XCD it runs on (k_step_split.h)
-                typedef unsigned long long u64;
-                __hip_atomic_store(reinterpret_cast<u64*>(diag_rw + cell0), ((u64)__float_as_uint(od[1]) << 32) | __float_as_uint(od[0]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (!cov_only)
-                    __hip_atomic_store(reinterpret_cast<u64*>(mean_rw + cell0), ((u64)__float_as_uint(om[1]) << 32) | __float_as_uint(om[0]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            store_vec<2>(diag_rw + cell0, od);
+            if (!cov_only) store_vec<2>(mean_rw + cell0, om);
         }
         // the m new rows (buffer stores through the item's resource: the row as scalar offset, lanes outside the rectangle out of
         // range -- no 64-bit address per lane and row).  (The loop stays in this function: handed on to a helper by reference, `acc`
@@ -202,31 +173,26 @@ __device__ __forceinline__ void ledger_close(const View& v, const AutoReset& ar,
     }
 }
 
-template <bool ONE>
-__device__ __forceinline__ void patch_sync() {
-    if (ONE) wave_lds_sync(); else __syncthreads();
-}
-
 // (KPN = 4 rows per request group: 12 workgroups of two waves per CU, 5 % faster for launches of 32768 items and 27 % slower for 4096
 // -- two-wave engines take it for large launches only, ipp_info.patch_big_min_items)
 // RJN: rounds of NW x 64 threads over the columns' rectangles (tests, compaction); 0 = enough for kPatchMaxRank.  An engine whose rank_cap
 // fits fewer rounds runs the instantiation without the empty ones (configs[2]: 1 of 3, the headline: 2 of 3 -- they are predicated
 // instructions otherwise, 2-3 % of an item's at configs[2], whose step is bound by the vector units).
-// BUD: the IPP_BUDGET form (fused step only, full-batch in-place launches): the ledger of ar.led is charged and closed per item, and with
+// BUD: the IPP_BUDGET form (full-batch in-place launches): the ledger of ar.led is charged and closed per item, and with
 // IPP_RESET_ON_DONE the envs it ends are reset in the launch (ledger_close).  The other instantiations do not contain a line of it.
-template <int NW, int KPN = kPatchKP, int MINW = kPatchMinW, bool SPLIT = false, int RJN = 0, bool BUD = false>
+template <int NW, int KPN = kPatchKP, int MINW = kPatchMinW, int RJN = 0, bool BUD = false>
 __global__ __launch_bounds__(64 * NW, MINW) void k_step_patch(
     View v, const int* __restrict__ env_ids, int n_items, const double* __restrict__ action,
     const double* __restrict__ prev_action, const float* __restrict__ meas_noise, unsigned flags,
     int* __restrict__ status_out, float* __restrict__ reward_out, AutoReset ar) {
     constexpr int MC = 9, VEC = 2, NT = kWave * NW, KP = KPN;
     static_assert(KPN <= kPatchKP, "the row lists are padded for kPatchKP entries");
+    static_assert(NW >= 2, "wave 0 runs the m x m algebra, wave 1 the observation");
     constexpr int RJ = RJN > 0 ? RJN : (kPatchMaxRank + NT - 1) / NT;  // rectangles per thread, loaded with the inputs
-    constexpr int OW = (NW > 1) ? 1 : 0;                   // the wave that evaluates the observation
+    constexpr int OW = 1;                                  // the wave that evaluates the observation
     constexpr int TW = (NW > 2) ? 2 : OW;                  // the wave that fills the small per-item tables (block cells, fp64 prior of the footprint)
-    constexpr bool ONE = (NW == 1);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_sp[];
-    const PatchLds lds(smem_sp, v.pcap, SPLIT ? 0 : v.plw * v.plw, SPLIT ? 1 : NW, v.punits, v.rank_cap);  // (split step: no prior table, one list area)
+    const PatchLds lds(smem_sp, v.pcap, v.plw * v.plw, NW, v.punits, v.rank_cap);
     if ((int)blockIdx.x >= n_items) return;
     const int item = launch_item(v, blockIdx.x, n_items);
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
@@ -234,10 +200,6 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_step_patch(
     IPP_WT_DECL;
     int* next_unit = lds.ctl; int* done_waves = lds.ctl + 1; int* solve_flag = lds.ctl + 2; int* obs_flag = lds.ctl + 3;
     int* wcnt = lds.ctl + 8;  // [RJ][NW] contributing columns found by wave w among its columns j
-    // split step: the item's block, indexed by the DISPATCH POSITION of this workgroup (the unit kernel maps its workgroups to
-    // positions the same way: no lookup of the item order in front of its first load)
-    float* blk = SPLIT ? v.blk + (size_t)(v.blk_pos0 + (int)blockIdx.x) * v.blk_stride : nullptr;
-    int* bh = reinterpret_cast<int*>(blk);
 
     // ------------------------------------------------------------------ batch 1: everything that does not depend on the footprint
     const int env0 = env_ids ? env_ids[item] : item + v.env_base;
@@ -252,7 +214,6 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_step_patch(
     double bud_ld = 0.0;
     int dep_ld = 0;
     if constexpr (BUD) { bud_ld = ar.led.budget[envc]; dep_ld = ar.led.depth[envc]; }
-    static_assert(!(BUD && SPLIT), "the budget ledger is a fused-step feature");
     const int* __restrict__ rects = v.colrect + (size_t)envc * v.rank_cap;
     unsigned rc_pre[RJ];
 #pragma unroll
@@ -267,7 +228,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_step_patch(
     const int R = v.window_rows;
     const PrepLds<MC> pl(lds.small);
     ItemHdr h;
-    if (ONE || __builtin_amdgcn_readfirstlane(wave) == 0) {
+    if (__builtin_amdgcn_readfirstlane(wave) == 0) {
         h = make_item_header<MC, IPP_FACTOR>(v, env0, env0, slots_ok, ax, ay, az, px, py, pz, rank_ld, sv_d, ls_d, flags);
         // rectangle of this step = its patch: rows / columns within R of the footprint, the column range widened to even columns
         const int r0 = max(0, h.yu - R), r1 = min(v.H - 1, h.yd + R);
@@ -281,10 +242,8 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_step_patch(
             lds.red[0] = 0.0; lds.red[1] = 0.0;
         }
     }
-    if (!ONE) {
-        __syncthreads();
-        if (__builtin_amdgcn_readfirstlane(wave) != 0) h = *pl.hs;
-    }
+    __syncthreads();
+    if (__builtin_amdgcn_readfirstlane(wave) != 0) h = *pl.hs;
     h = uniform_hdr(h);
     IPP_EXIT_POINT(1);
     const int r0n = max(0, h.yu - R), r1n = min(v.H - 1, h.yd + R);
@@ -296,9 +255,8 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_step_patch(
             v.hdr[item] = h;
             if (status_out) status_out[item] = h.status;
             reward_out[item] = 0.f;
-            if (SPLIT) { bh[SplitBlk::ITEM] = item; bh[SplitBlk::NUNITS] = 0; }  // (no unit runs)
         }
-        patch_sync<ONE>();  // (every thread holds its copy of prev_action)
+        __syncthreads();  // (every thread holds its copy of prev_action)
         if ((flags & IPP_UPDATE_PREV) && tid == 0) {
             double* pw = const_cast<double*>(prev_action);
             pw[3 * item + 0] = ax; pw[3 * item + 1] = ay; pw[3 * item + 2] = az;
@@ -308,7 +266,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_step_patch(
             if (k >= 0 && h.env >= 0 && h.env < v.cap) wave_reset_env(v, ar, h.env, k, tid);
         }
         if constexpr (BUD) {
-            if (tid < kWave) ledger_close(v, ar, flags, h.env, item, v.blk_pos0 + (int)blockIdx.x, bud_ld, dep_ld, h.cost_d, tid);
+            if (tid < kWave) ledger_close(v, ar, flags, h.env, item, v.pos0 + (int)blockIdx.x, bud_ld, dep_ld, h.cost_d, tid);
         }
         return;
     }
@@ -317,11 +275,9 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_step_patch(
     const float* mean_env = v.mean + (size_t)h.env * v.Npad;
     const float* gt_env = gt_plane(v, h.env);
     float* slot = v.cov + (size_t)h.env * v.cov_slot;
-    // records that do not fit the LDS staging: the item's global scratch block (split step: the record area of the item's block, which
-    // receives EVERY record -- record a at blk_rec + a * 16 -- the first pcap of them are staged in LDS as well, for the m x m algebra)
-    float* blk_rec = SPLIT ? blk + SplitBlk::rec_off(v.plw) : nullptr;
+    // records that do not fit the LDS staging: the item's global scratch block
     const int cap = v.pcap, pw = v.pw;
-    float* ovf = SPLIT ? blk_rec + (size_t)cap * kPatchRec : v.q + (size_t)item * v.q_item;
+    float* ovf = v.q + (size_t)item * v.q_item;
 
     // ------------------------------------------------------------------ batch 2: inputs of the observation (lanes of wave OW)
     ObsRegs oregs;
@@ -349,7 +305,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_step_patch(
         const int r0k = rc & 0xff, r1k = (rc >> 8) & 0xff, c0k = (rc >> 16) & 0xff, c1k = rc >> 24;
         con[j] = k < r && r0k <= h.yd && r1k >= h.yu && c0k <= h.xr && c1k >= h.xl;
         bal[j] = __ballot(con[j]);
-        if (!ONE && lane == 0) wcnt[j * NW + wave] = __popcll(bal[j]);
+        if (lane == 0) wcnt[j * NW + wave] = __popcll(bal[j]);
     }
     const int ttid = tid - kWave * TW;
     if (ttid >= 0 && ttid < MC) {  // measurement blocks of the footprint as flat (cell, weight) tables + the tables of the m x m algebra
@@ -363,7 +319,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_step_patch(
         }
         if (ttid < m) { pl.bcnt[ttid] = bb.count(); pl.bwt[ttid] = bb.weight; }
     }
-    patch_sync<ONE>();
+    __syncthreads();
     if (tid == 0) IPP_MARK(item, 4);
     IPP_EXIT_POINT(2);
     int pos[RJ];
@@ -371,15 +327,11 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_step_patch(
 #pragma unroll
     for (int j = 0; j < RJ; ++j) {
         int before = 0, all = 0;
-        if (ONE) {
-            all = __popcll(bal[j]);
-        } else {
 #pragma unroll
-            for (int w = 0; w < NW; ++w) {
-                const int c = wcnt[j * NW + w];
-                before += (w < wave) ? c : 0;
-                all += c;
-            }
+        for (int w = 0; w < NW; ++w) {
+            const int c = wcnt[j * NW + w];
+            before += (w < wave) ? c : 0;
+            all += c;
         }
         pos[j] = n_c + before + __popcll(bal[j] & ((1ull << lane) - 1ull));
         n_c += all;
@@ -394,7 +346,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_step_patch(
 #pragma unroll
     for (int j = 0; j < RJ; ++j)
         if (con[j]) { klist[pos[j]] = (unsigned short)(tid + j * NT); rclist[pos[j]] = rc_pre[j]; }
-    patch_sync<ONE>();
+    __syncthreads();
     // (no barrier behind the reads: nothing below writes the two lists' areas before the barrier that ends the gather -- the
     // records go to lds.rec, the prior tables to lds.lut and pl.ktab, which starts behind the rectangle list)
     static_assert(4 * kPatchMaxRank <= (3 * MC * (MC + 1) + 3 * MC + 4 * MC) * 8, "rectangle list reaches pl.ktab");
@@ -404,8 +356,8 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_step_patch(
     // unconditional buffer load whose offset is pushed out of range where the column is not stored.  The waves of the item SHARE
     // a round: wave w takes the measurement blocks i = w (mod NW) of all its columns and writes those entries of the records -- with
     // the usual 30-60 contributing columns one wave issued all 9 .. 36 requests per column while the others waited at the barrier.
-    const int wave_u = ONE ? 0 : __builtin_amdgcn_readfirstlane(wave);
-    auto mine = [&](int i) { return ONE || (i % NW) == wave_u; };
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    auto mine = [&](int i) { return (i % NW) == wave_u; };
     const auto slot_rs = __builtin_amdgcn_make_buffer_rsrc(slot, 0, 0x7ffffff0, 0x00020000);
     const auto row_rs = __builtin_amdgcn_make_buffer_rsrc(slot - v.pstride, 0, 0x7ffffff0, 0x00020000);  // (records hold offsets from here)
     // (cells and weights of the measurement blocks from the LDS tables filled in front of the barrier above: evaluating
@@ -442,7 +394,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_step_patch(
     auto gather_store = [&](unsigned rc, int k, bool on, int a_pos, const float (&l)[MC][4]) {
         if (!on) return;
         float* dst = (a_pos < cap) ? lds.rec + (size_t)a_pos * kPatchRec : nullptr;
-        float* gdst = (SPLIT || a_pos >= cap) ? (SPLIT ? blk_rec + (size_t)a_pos * kPatchRec : ovf + (size_t)(a_pos - cap) * kPatchRec) : nullptr;
+        float* gdst = (a_pos >= cap) ? ovf + (size_t)(a_pos - cap) * kPatchRec : nullptr;
 #pragma unroll
         for (int i = 0; i < MC; ++i) {
             if (i < m && mine(i)) {
@@ -483,11 +435,10 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_step_patch(
         {
             const float s3 = prior_scale_f(v.prior_kind, v.res, h.ls);
             const int lw = v.plw;
-            float* lut_dst = SPLIT ? blk + SplitBlk::kTab + SplitBlk::kTabFixed : lds.lut;  // (split step: straight into the item's block)
             with_prior_kind(v.prior_kind, [&](auto kind) {
                 for (int i = tid; i < lw * lw; i += NT) {
                     const int dr = div_small(i, lw), dc = i - dr * lw;
-                    lut_dst[i] = prior_f<decltype(kind)::value>(dr, dc, s3, h.sv);
+                    lds.lut[i] = prior_f<decltype(kind)::value>(dr, dc, s3, h.sv);
                 }
             });
             if (ttid >= 0 && ttid < f) { const int ky = div_small(ttid, h.w); pl.ktab[ttid] = prior_d(v.prior_kind, ky, ttid - ky * h.w, v.res, sv_d, ls_d); }
@@ -512,24 +463,15 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_step_patch(
     }
     const int n_lds = min(n_c, cap), n_ovf = n_c - n_lds;
     if (n_ovf > 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // overflow records are read back by the other waves
-    patch_sync<ONE>();
+    __syncthreads();
     if (tid == 0) IPP_MARK(item, 1);
     IPP_WT(6);
     IPP_EXIT_POINT(3);
 
     // ------------------------------------------------------------------ m x m algebra (wave 0) / observation (wave OW)
-    float* linv_dst = SPLIT ? blk + SplitBlk::kTab + 72 : lds.Ls;  // (split step: L^-1 | y straight into the item's block)
     int status_w0 = 0;  // (wave 0: the status of the m x m algebra)
-    if (ONE) {
-        observe_wave<MC>(v, h, flags, lds.small, oregs);
-        status_w0 = solve_wave_fast<MC>(v, h, item, flags, lds.small, lds.rec, 1, kPatchRec, linv_dst, linv_dst + 81, nullptr, status_out,
-                                        nullptr, n_lds, n_ovf > 0 ? ovf : nullptr, n_ovf);
-        wave_lds_sync();
-        if (lane == 0) *solve_flag = (status_w0 == IPP_STATUS_NOT_PD) ? 2 : 1;
-        wave_lds_sync();
-        if (lane == 0) IPP_MARK(item, 7);
-    } else if (wave == 0) {
-        status_w0 = solve_wave_fast<MC>(v, h, item, flags, lds.small, lds.rec, 1, kPatchRec, linv_dst, linv_dst + 81, nullptr, status_out,
+    if (wave == 0) {
+        status_w0 = solve_wave_fast<MC>(v, h, item, flags, lds.small, lds.rec, 1, kPatchRec, lds.Ls, lds.ys, nullptr, status_out,
                                         obs_flag, n_lds, n_ovf > 0 ? ovf : nullptr, n_ovf);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         if (lane == 0) __hip_atomic_store(solve_flag, status_w0 == IPP_STATUS_NOT_PD ? 2 : 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -544,28 +486,6 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_step_patch(
     const UnitGeo ug = unit_geometry(r0n, c0n, hn, wn);
     const int n_units = ug.n_units;
 
-    if constexpr (SPLIT) {
-        // ---------------------------------------------------------------- split step: the rest of the item's block (wave 0), and out
-        if (!ONE && __builtin_amdgcn_readfirstlane(wave) != 0) return;
-        const bool dead_p = status_w0 == IPP_STATUS_NOT_PD;
-        if (lane < 4 * MC) {  // footprint tables of the units' prior term
-            bh[SplitBlk::kTab + lane] = lds.fb_yx[lane];
-            blk[SplitBlk::kTab + 36 + lane] = lds.fb_w[lane];
-        }
-        if (lane == 0) {
-            bh[SplitBlk::ITEM] = item; bh[SplitBlk::ENV] = h.env; bh[SplitBlk::M] = m; bh[SplitBlk::NC] = n_c;
-            bh[SplitBlk::NUNITS] = n_units; bh[SplitBlk::RANK] = r;
-            bh[SplitBlk::BITS] = ((h.rf == 1) ? SplitBlk::B_RF1 : 0) | ((h.commit != 0) ? SplitBlk::B_COMMIT : 0) | (dead_p ? SplitBlk::B_DEAD : 0);
-            bh[SplitBlk::RECT] = (int)rect_pack(r0n, r1n, c0n, c1n);
-            bh[SplitBlk::TSPAN] = pl.hs->t_lo | (pl.hs->t_hi << 16);
-            bh[SplitBlk::RESET] = ar.src ? ar.src[item] : -1;
-            const double cost_d = pl.hs->cost_d;
-            bh[SplitBlk::COST_LO] = __double2loint(cost_d); bh[SplitBlk::COST_HI] = __double2hiint(cost_d);
-            bh[SplitBlk::kSync] = 0;  // arrival counter of the units
-            IPP_MARK(item, 2);
-        }
-        return;
-    } else {
     // rectangles and patch offsets of the first 128 records, record a in lane a & 63 of set a >> 6 (read by the unit loop through
     // v_readlane: no LDS round trip per stored row)
     const int n_fast = min(n_lds, 2 * kWave);
@@ -588,7 +508,6 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_step_patch(
     io.mean_rw = v.mean + (size_t)env_u * v.Npad;
     io.diag_rw = v.diag + (size_t)env_u * v.Npad;
     io.cov_only = cov_only;
-    io.wt_planes = false;
     io.m = m;
     io.row0_bytes = (r + 1) * v.pstride * 4;  // first new row, from one patch in front of the slot (row_rs)
     io.pstride_bytes = v.pstride * 4;
@@ -643,11 +562,10 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_step_patch(
         v.colspan[(size_t)env_u * v.rank_cap + r + lane] = t_span;
         v.colrect[(size_t)env_u * v.rank_cap + r + lane] = (int)rect_pack(r0n, r1n, c0n, c1n);
     }
-    if constexpr (BUD) ledger_close(v, ar, flags, env_u, item, v.blk_pos0 + (int)blockIdx.x, bud_ld, dep_ld, cost_d, lane);  // (after the rank store above, same lane 0)
+    if constexpr (BUD) ledger_close(v, ar, flags, env_u, item, v.pos0 + (int)blockIdx.x, bud_ld, dep_ld, cost_d, lane);  // (after the rank store above, same lane 0)
     else if (reset_k >= 0) wave_reset_env(v, ar, env_u, reset_k, lane);  // (after the rank store above, same lane 0)
     IPP_WT(8);
     IPP_WT_FLUSH(lane);
-    }
 }
 
 // Patch-layout factor state -> dense P = P0 - U U^T (ipp_read_cov_dense: tests, np.diag(state), feature planes).

@@ -410,14 +410,3 @@ def test_baseline_configs_take_the_patch_kernels(grid, capacity, T, node_capacit
     assert eng.info.patch_layout == 1 and eng.info.fused_step == 1 and eng.info.patch_waves == 3
     assert eng.info.patch_two_wave_min_items == 6144 and eng.info.patch_big_min_items == 16384
     eng.close()
-
-
-def test_two_wave_engines_keep_their_large_launch_instantiation(monkeypatch):
-    """IPP_PATCH_WAVES=2 (the round-3 configuration, kept for A/B): launches of >= 16384 items take k_step_patch<2, 4, 6>."""
-    from ipp_rl_amd import EngineConfig, IPPEngine
-
-    fresh_gpu()
-    monkeypatch.setenv("IPP_PATCH_WAVES", "2")
-    eng = IPPEngine(EngineConfig(x_dim=50, y_dim=50), capacity=64, state="factor", rank_cap=360, window_rows=-1, fixed_prior=True)
-    assert eng.info.patch_waves == 2 and eng.info.patch_big_min_items == 16384 and eng.info.patch_two_wave_min_items == 0
-    eng.close()

@@ -1,7 +1,7 @@
 """
 GPU tests of the prior kinds (include/ipp_engine.h IPP_PRIOR_*: Matern nu = 0.5, 2.5 and inf next to the default 1.5) on every
 route a public default reaches: dense and shuffled resets, Mapping.update_grid_map (dense compat engine), exact and windowed
-factor engines (one launch, two groups on two queues, the split step), ipp_score_actions, ipp_tree_step and VecIPPEnv.
+factor engines (one launch, two groups on two queues), ipp_score_actions, ipp_tree_step and VecIPPEnv.
 References: the reference's priors and episodes for each nu (tests/golden/priors_nu.npz, gen_prior_golden.py) and the dense
 NumPy Kalman step of oracle/ipp_oracle.py started from the closed-form prior.  Tolerance 1e-5 (fp32 device state).
 """
@@ -125,23 +125,19 @@ def replay(eng, g15, g, k, env=0):
     assert np.max(np.abs(host(eng.read_cov(env))[g15["sample_rows"]] - g[k + "P_final_rows"])) < TOL
 
 
-@pytest.mark.parametrize("window_rows,split", [(0, None), (-1, "0"), (-1, "1")])
+@pytest.mark.parametrize("window_rows,split", [(0, None), (-1, "0")])
 @pytest.mark.parametrize("prefix,nu", NUS)
 def test_factor_engines_replay_the_50x50_episode(golden, monkeypatch, prefix, nu, window_rows, split):
-    """Exact columns (k_gain_factor) and the smallest fixed-prior window of the kind (patch layout: the fused patch step, and
-    the split step under IPP_SPLIT=1) replay episode_rf1_50_s0 of that prior."""
+    """Exact columns (k_gain_factor) and the smallest fixed-prior window of the kind (patch layout: the fused patch step)
+    replay episode_rf1_50_s0 of that prior."""
     from ipp_rl_amd import IPPEngine
 
     name = "episode_rf1_50_s0"
     g15, g = golden(name), golden("priors_nu")
-    if split is not None:
-        monkeypatch.setenv("IPP_SPLIT", split)  # read by ipp_engine_create
     eng = IPPEngine(cfg_of(nu, 50), capacity=2, state="factor", rank_cap=360, window_rows=window_rows, fixed_prior=True)
-    if split is not None:
-        monkeypatch.delenv("IPP_SPLIT")
     if window_rows < 0:
         assert int(eng.info.window_rows) == MIN_FIXED[nu] and int(eng.info.patch_layout) == 1
-        assert int(eng.info.patch_split_min_items) == int(split)
+        assert int(eng.info.patch_split_min_items) == 0
     replay(eng, g15, g, prefix + name + "_", env=1)
     eng.close()
 

@@ -11,15 +11,6 @@ for k in 10 20 50 200; do python bench.py --full --no-cpu-baseline --no-extra --
 import json,sys
 d=json.loads(sys.stdin.read()); c=d['config']
 print('steps', d['steps'], 'value %.2f M' % (d['value']/1e6), 'ms/step %.4f' % d['ms_per_step'], 'host issue %.4f' % (c.get('host_issue_ms_per_step') or 0), 'regions', ['%.4f' % x for x in c['region_ms_per_step']])"; done > $O/region_sweep.txt 2>&1; cat $O/region_sweep.txt
-# the split step (prologue kernel + unit kernel) against the fused kernel (round 5's question; ROUND_SPLIT=1 repeats it)
-if [ "$ROUND_SPLIT" = "1" ]; then
-# the split step (prologue kernel + unit kernel) against the fused kernel, same box: headline, one launch per step, configs[2], configs[3] share
-{ CFG="--parts 2" bash tools/ab_cfg.sh "IPP_SPLIT=0" "IPP_SPLIT=1" "IPP_SPLIT=1 IPP_SPLIT_WAVES=1"
-  CFG="--parts 1 --steps 100" bash tools/ab_cfg.sh "IPP_SPLIT=0" "IPP_SPLIT=1" "IPP_SPLIT=1 IPP_SPLIT_WAVES=1"
-  CFG="--grid 100 --envs 32768 --episode-steps 16 --steps 20 --warmup 4" bash tools/ab_cfg.sh "IPP_SPLIT=0" "IPP_SPLIT=1 IPP_SPLIT_WAVES=1"
-  CFG="--grid 50 --envs 32768 --steps 20 --warmup 4" bash tools/ab_cfg.sh "IPP_SPLIT=0" "IPP_SPLIT=1 IPP_SPLIT_WAVES=1"; } > $O/ab_split.txt 2>&1
-[ -f tools/probes/libipp_timing.so ] && { for w in 1 3; do echo "=== split step, prologue kernel with $w waves per item, 2 groups"; IPP_SPLIT_WAVES=$w python tools/timeline_split.py 2 2>&1 | grep -v amdgpu.ids | head -40; done; } > $O/timeline_split.txt 2>&1
-fi
 # round 6: the arena's origin (torch tensor against the virtual-memory API), fresh processes on the driver's protocol
 bash tools/ab_arena.sh > /dev/null 2>&1; cp gpurun_out/arena/ab_arena.txt $O/ab_arena.txt
 {
@@ -44,12 +35,6 @@ timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_mct
 # PMC passes (separate runs, counters only)
 bash tools/pmc_run.sh $O/pmc --parts 1 > $O/pmc_run.log 2>&1
 python tools/pmc_summary.py $O/pmc 40 > $O/pmc_summary.json 2>$O/pmc_summary.err; head -c 120 $O/pmc_summary.json
-if [ "$ROUND_SPLIT" = "1" ]; then
-# the split step's kernels (unit kernel: waves' wait share, traffic; prologue kernel) -- its summary is NOT named *pmc_summary*: bench.py
-# replays traffic from those, and the split run has the same command line
-IPP_SPLIT=1 PMC_CUSTOM="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAVES;FETCH_SIZE;WRITE_SIZE TCC_HIT_sum TCC_MISS_sum;SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU" bash tools/pmc_run.sh $O/pmc_split --parts 1 > $O/pmc_run_split.log 2>&1
-python tools/pmc_summary.py $O/pmc_split 40 > $O/split_pmc.json 2>>$O/pmc_summary.err
-fi
 PMC_SETS=traffic bash tools/pmc_run.sh $O/pmc_w12 --parts 1 --shuffle-prior > $O/pmc_run_w12.log 2>&1
 python tools/pmc_summary.py $O/pmc_w12 40 > $O/pmc_summary_w12.json 2>>$O/pmc_summary.err
 bash tools/pmc_run.sh $O/pmc_cfg2 --parts 1 --grid 100 --envs 32768 --episode-steps 16 --steps 20 --warmup 4 > $O/pmc_run_cfg2.log 2>&1

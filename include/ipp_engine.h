@@ -72,6 +72,9 @@ typedef struct ipp_field_record {
                                 /* restarts and refill[position] names it for ipp_generate_grf_refill                           */
 #define IPP_BUDGET_STREAM (3ull << 40) /* Philox subsequence base of the shuffled start budgets: episode j of global env g draws  */
                                        /* its budget from subsequence IPP_BUDGET_STREAM + j, counter g                          */
+#define IPP_CMA_STREAM    (9ull << 40) /* Philox subsequence base of the CMA-ES planner's normals: generation g of a policy's r-th  */
+                                       /* replan draws row (global env id) of subsequence IPP_CMA_STREAM + r * max_iter + g; the    */
+                                       /* bases 1..8 << 40 are the ground-truth, noise, budget, self-play and replay streams          */
 
 /* per-item status written by ipp_step */
 #define IPP_STATUS_OK            0
@@ -968,6 +971,61 @@ int ipp_pvnet_loss(const float* logits, const float* target_policy, const uint8_
 #define IPP_PVNET_SGD_SCRATCH 1024
 int ipp_pvnet_sgd_step(float* params, const float* grads, float* momentum_buf, int64_t n, double lr, double momentum, double weight_decay,
                        double max_norm, double* norm_out, double* scratch, uint64_t scratch_doubles, int32_t device, void* stream);
+
+/*
+ * Batched CMA-ES (the reference's planning/ipp_masha.py: cma.CMAEvolutionStrategy with ask / tell around simulate_trajectory,
+ * :160-178): one independent (mu/mu_w, lambda)-CMA-ES per env, Hansen's "The CMA Evolution Strategy: A Tutorial" with its default
+ * parameters and positive recombination weights only, in fp64; no handle, bare [dev] buffers, one wavefront per env.  Every env has its
+ * OWN dimension N_e in [0, nmax], nmax <= IPP_CMA_MAX_DIM; an env of dimension 0 and an env whose status is not 0 are skipped by every
+ * call.  The population lam in [4, IPP_CMA_MAX_LAMBDA] is shared by a launch.  Divergences from the cma package:
+ * no boundary transform, no stopping tests, an eigendecomposition every generation, positive weights, Philox normals.
+ *
+ * State of one env: ipp_cma_state_bytes / 8 words of 8 bytes, with NM = nmax, in this order: m double[NM], sigma, C double[NM][NM],
+ * B double[NM][NM] (eigenvectors in columns), D double[NM] (square roots of the eigenvalues), p_sigma double[NM], p_c double[NM],
+ * best-ever x double[NM], best-ever f, then int64 generation, status (0 ok, 1 breakdown, 2 a dimension outside [0, nmax]), dimension.
+ */
+#define IPP_CMA_MAX_DIM    48
+#define IPP_CMA_MAX_LAMBDA 64
+int ipp_cma_state_bytes(int32_t nmax, uint64_t* bytes /*[host] out: per env*/);
+/* Start state (cma.CMAEvolutionStrategy(x0, sigma0 = 1), ipp_masha.py:162-171): m = m0 [dev] double[n][nmax], sigma = 1, C = B = I,
+ * D = 1, both paths 0, generation 0, best-ever (m0, +inf); dims [dev] int32[n]. */
+int ipp_cma_init(void* state /*[dev]*/, int32_t n, int32_t nmax, const int32_t* dims, const double* m0, int32_t device, void* stream);
+/* cma_es.ask (ipp_masha.py:174): x [dev] double[n][lam][nmax], x[e][k][:N_e] = m + sigma scale (.) (B (D (.) z_k)) with z_k =
+ * normals[e][k][:N_e] ([dev] float[n][lam][nmax], e.g. from ipp_fill_normal_rows) and scale [dev] double[nmax] the per-coordinate
+ * standard deviations (CMA_stds, :151-156); coordinates from N_e on are 0. */
+int ipp_cma_ask(const void* state, int32_t n, int32_t nmax, int32_t lam, const float* normals, const double* scale, double* x, int32_t device,
+                void* stream);
+/*
+ * What the evaluation of simulate_trajectory (ipp_masha.py:102-140) needs, for per_env candidates x [dev] double[n][per_env][nmax] of
+ * each env (dims [dev] int32[n]: 3 x the waypoints of env e's candidates, at most `horizon` of them are used), from the env's waypoint
+ * prev [dev] double[n][3] and remaining budget [dev] double[n]:
+ *   out_of_bounds (planning/common/actions.py:102-106) of every waypoint, inclusive on both ends: waypoint[0] in [0, x_hi],
+ *     waypoint[1] in [0, y_hi], waypoint[2] in [z_lo, z_hi] (the reference tests waypoint[0] against y_dim * resolution and
+ *     waypoint[1] against x_dim * resolution: pass them so);
+ *   cost [dev] double[horizon][n * per_env]: action_costs (actions.py:8-41) of every step, Euclidean or the trapezoidal flight time;
+ *   path [dev] double[n * per_env]: their sum over all of the candidate's waypoints (:108-112);
+ *   live [dev] int32[n * per_env]: the steps before the first one whose cost exceeds the running remaining budget (:122-125; a
+ *     zero-cost step is live), -1 for a candidate out of bounds, -2 for a path cost <= 0;
+ *   action, prev_action [dev] double[horizon][n * per_env][3]: the rows of the covariance-only step launch of step t; a step that
+ *     is not live has a NaN action, which the step applies nothing for.
+ */
+int ipp_cma_plan(const int32_t* dims, const double* x, const double* prev, const double* budget, int32_t n, int32_t per_env, int32_t nmax,
+                 int32_t horizon, double x_hi, double y_hi, double z_lo, double z_hi, int32_t use_flight_time, double max_v, double max_a,
+                 double* action, double* prev_action, double* cost, double* path, int32_t* live, int32_t device, void* stream);
+/* The objective (ipp_masha.py:104-106, :114-115, :135-140) from the step launches' reward [dev] float[horizon][candidates] and status
+ * [dev] int32[horizon][candidates]: f [dev] double[candidates] = 100 for a candidate out of bounds, of path cost <= 0 or with a live
+ * step whose status is neither IPP_STATUS_OK nor the Cholesky fallback, else -(sum over live steps of reward (cost + 1)) / path. */
+int ipp_cma_objective(const float* reward, const int32_t* status, const double* cost, const double* path, const int32_t* live,
+                      int32_t candidates, int32_t horizon, double* f, int32_t device, void* stream);
+/*
+ * cma_es.tell (ipp_masha.py:175) from the fitness f [dev] double[n][lam] of the candidates x that ipp_cma_ask made of normals: ranking
+ * (ascending, ties to the lower index, NaN as +inf), m, p_sigma, h_sigma, p_c, C and sigma by the tutorial's equations with the
+ * constants of (N_e, lam), C symmetrised and eigendecomposed by a cyclic Jacobi in a fixed pair order (C = B diag(D^2) B^T), the
+ * best-ever (x, f) replaced only by a strictly smaller f.  A new eigenvalue that is not finite and positive, or a sigma that is not
+ * finite, sets status = 1 and keeps the previous m, B and D.  Deterministic: no atomics, every sum in a fixed order.
+ */
+int ipp_cma_tell(void* state, int32_t n, int32_t nmax, int32_t lam, const float* normals, const double* x, const double* f, const double* scale,
+                 int32_t device, void* stream);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,8 @@ IPP_PRIOR_MATERN32, IPP_PRIOR_MATERN12, IPP_PRIOR_MATERN52, IPP_PRIOR_RBF = 0, 1
 IPP_COV_ONLY, IPP_PREDICT_ONLY, IPP_ADAPTIVE, IPP_USE_FLIGHT_TIME, IPP_GIVEN_OBSERVATION, IPP_UPDATE_PREV = 1, 2, 4, 8, 16, 32
 IPP_BUDGET, IPP_RESET_ON_DONE = 64, 128
 IPP_BUDGET_STREAM = 3 << 40
+IPP_CMA_STREAM = 9 << 40  # Philox subsequence base of the CMA-ES planner's normals (planning/vec_cmaes.py)
+IPP_CMA_MAX_DIM, IPP_CMA_MAX_LAMBDA = 48, 64
 # Philox subsequence bases of the self-play draws (ipp_selfplay_record / _commit, ipp_replay_gather)
 IPP_SP_ACTION_STREAM, IPP_SP_INIT_STREAM, IPP_SP_TIE_STREAM, IPP_SP_ARGMAX_STREAM, IPP_REPLAY_STREAM = (4 << 40, 5 << 40, 6 << 40, 7 << 40,
                                                                                                        8 << 40)
@@ -213,6 +215,14 @@ PROTOTYPES = {
                                  _P, _P, _P, _P, C.c_int32, _P]),
     "ipp_pvnet_sgd_step": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, C.c_uint64,
                                      C.c_int32, _P]),
+    # (the batched CMA-ES planner's calls, csrc/k_cmaes.h: bare buffers, no handle; added without an ABI bump as well)
+    "ipp_cma_state_bytes": (C.c_int, [C.c_int32, C.POINTER(C.c_uint64)]),
+    "ipp_cma_init": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P]),
+    "ipp_cma_ask": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P]),
+    "ipp_cma_plan": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
+                               C.c_int32, C.c_double, C.c_double, _P, _P, _P, _P, _P, C.c_int32, _P]),
+    "ipp_cma_objective": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
+    "ipp_cma_tell": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, _P]),
 }
 
 _lib = None

@@ -1,1 +1,2 @@
 from .vec_greedy import VecGreedyPolicy  # noqa: F401
+from .vec_cmaes import VecCmaesPolicy  # noqa: F401

@@ -186,11 +186,15 @@ class VecGreedyPolicy:
         (waypoints [n, horizon, 3], valid [n, horizon]); the envs themselves are not written."""
         env, torch = self.env, self.env.torch
         eng = env.engine
-        ids = torch.as_tensor(np.asarray(env_ids), dtype=torch.int32, device=env.device)
-        sids = torch.as_tensor(np.asarray(scratch_ids), dtype=torch.int32, device=env.device)
+        def dev(x, dtype):  # (device tensors pass through: a caller that holds them does not read them back)
+            if isinstance(x, torch.Tensor):
+                return x.to(device=env.device, dtype=dtype)
+            return torch.as_tensor(np.asarray(x), dtype=dtype, device=env.device)
+
+        ids, sids = dev(env_ids, torch.int32), dev(scratch_ids, torch.int32)
         eng.fork(ids, sids)
         prev = env.prev[ids.long()].clone()
-        left = torch.as_tensor(np.asarray(budget, dtype=np.float64), dtype=torch.float64, device=env.device).clone()
+        left = dev(budget, torch.float64).clone()
         alive = torch.ones(ids.numel(), dtype=torch.bool, device=env.device)
         ways, valids = [], []
         for _ in range(int(horizon)):

@@ -887,6 +887,61 @@ int ipp_replay_gather_rows(const ipp_selfplay* sp, int32_t n, int32_t channels, 
 int ipp_replay_priority_update(const ipp_selfplay* sp, double* priority, const int64_t* index, const double* value, int32_t n,
                                void* stream);
 
+/*
+ * Playing with a trained network (csrc/k_play.h): the decision of the deployment planner, MCTSZeroMission.replan,
+ * planning/mcts_zero/mcts_zero_mission.py:504-523 (`workers` root-parallel searches per decision, their policies summed, normalised,
+ * arg-max), and the game bookkeeping of the arena gate, planning/mcts_zero/arenas.py:25-56, for every env of a budget-mode batch at once.
+ * The search has `workers` roots per env: root e workers + w is worker w of env e.  Draws as for ipp_selfplay (global env id g = e +
+ * row_offset).  All pointers [dev], caller-owned.
+ */
+typedef struct ipp_play {
+    int32_t num_envs;        /* B: env slots                                                                         */
+    int32_t workers;         /* searches per env and decision (num_workers), >= 1                                    */
+    int32_t kmax;            /* width of the valid-action rows (ipp_mcts_tables.kmax), <= 2048                       */
+    int32_t num_actions;     /* A                                                                                    */
+    int32_t games_per_env;   /* G: episodes counted per env, >= 1                                                    */
+    int32_t tie_rule;        /* 0 deploy: first maximiser (np.argmax, :522); 1 arena: IPP_SP_ARGMAX_STREAM draw among the maxima */
+    int32_t device;
+    int32_t reserved;
+    double  gamma;
+    uint64_t seed;
+    int64_t row_offset;      /* global id of env slot 0                                                              */
+    const double* actions;   /* [A][3] waypoints in the reference's enumeration                                      */
+    /* the env batch's ledger (ipp_set_budget) and step outputs, per env */
+    double* budget; int32_t* depth; int64_t* episode; uint8_t* done; double* prev; const float* reward;
+    /* per env: running discounted return and steps of the running game, games counted so far, forced end of this step, next step's tie
+     * uniform, the step's action [B][3] and its index (-1: none) */
+    double* ret; int32_t* steps; int32_t* games; uint8_t* forced; double* tie_u; double* action; int32_t* action_idx;
+    /* per game [B][G]: the discounted return (arenas.py:38, :45) and the number of steps of the env's g-th game */
+    double* game_value; int32_t* game_steps;
+    double* ensemble;        /* [B][kmax] the normalised summed policy on the valid set (zeros for an env without a decision), or NULL */
+} ipp_play;
+
+/*
+ * The decision of replan (mcts_zero_mission.py:516-523) before the env step.  policy [dev] [B workers][kmax], valid_idx [dev] [B workers]
+ * [kmax], ok [dev] [B workers]: ipp_mcts_policy's outputs for the B workers roots.  The env's valid set is the row of its first worker with
+ * ok != 0 (all workers share waypoint and budget).  total[k] = the sum over the workers with ok != 0, in worker order, of policy[..][k] on
+ * the slots with valid_idx >= 0 (:516-519); ensemble = total / sum_k total[k], the sum in ascending k (:521); the action is a maximiser of
+ * the ensemble (:522): tie_rule 0 the first one, tie_rule 1 the one ipp_selfplay_record's temperature-0 step draws (mcts.py:134-138:
+ * IPP_SP_ARGMAX_STREAM + episode at counter (g << 20) + depth).  Writes action_idx[e], action[e] = its waypoint and forced[e] = 0.  An
+ * env with no worker ok, a NaN among the summed values, a sum or maximum that is not positive and finite, or a chosen valid index outside
+ * [0, num_actions) ends its episode as in ipp_selfplay_record: budget[e] <- 0, action[e] <- prev[e], action_idx[e] <- -1, forced[e] <- 1.
+ */
+int ipp_play_pick(const ipp_play* pl, const double* policy, const int32_t* valid_idx, const int32_t* ok, void* stream);
+/*
+ * After the budget step: the bookkeeping of Arena.play_game (arenas.py:32-45).  An env that is not forced: ret += gamma^steps reward
+ * (:38; the power as in ipp_selfplay_commit), steps += 1; a forced step adds nothing.  An env whose episode ended (done or forced): if
+ * games[e] < games_per_env, game_value[e][games[e]] = ret, game_steps[e][games[e]] = steps, games[e] += 1 (later episodes are played but
+ * not counted); ret = 0, steps = 0.  tie_u[e] for the next step as ipp_selfplay_commit writes it (IPP_SP_TIE_STREAM).
+ */
+int ipp_play_tally(const ipp_play* pl, void* stream);
+/*
+ * Arena.play_games' totals (arenas.py:47-56) over the counted games: out [dev] double [4] = the sum of their game_value, their number, the
+ * sum of their game_steps, the number of envs with games == games_per_env.  Fixed order: with i = e games_per_env + g, partial sum l
+ * (0 <= l < 64) adds the counted items l, l + 64, ... in ascending order; the partial sums are added in the order l = 0 .. 63.
+ */
+int ipp_play_totals(const ipp_play* pl, double* out, void* stream);
+
 /* ---- Policy-value network ------------------------------------------------------------------------------------------------------
  * Inference of the reference's PolicyValueNetwork (planning/mcts_zero/networks/policy_value_networks.py:12-69 on the layers of
  * planning/common/layers.py) as a PLAN: a flat list of op records over one packed fp32 weight blob, built on the host by

@@ -122,6 +122,18 @@ class IppSelfPlay(C.Structure):
         ("r_policy", _P), ("r_idx", _P), ("r_value", _P), ("r_reward", _P), ("r_flags", _P),
     ]
 
+
+class IppPlay(C.Structure):
+    """ipp_play (include/ipp_engine.h): the deployment planner's / arena's per-env decision and game bookkeeping, [dev] pointers."""
+    _fields_ = [
+        ("num_envs", C.c_int32), ("workers", C.c_int32), ("kmax", C.c_int32), ("num_actions", C.c_int32),
+        ("games_per_env", C.c_int32), ("tie_rule", C.c_int32), ("device", C.c_int32), ("reserved", C.c_int32),
+        ("gamma", C.c_double), ("seed", C.c_uint64), ("row_offset", C.c_int64),
+        ("actions", _P), ("budget", _P), ("depth", _P), ("episode", _P), ("done", _P), ("prev", _P), ("reward", _P),
+        ("ret", _P), ("steps", _P), ("games", _P), ("forced", _P), ("tie_u", _P), ("action", _P), ("action_idx", _P),
+        ("game_value", _P), ("game_steps", _P), ("ensemble", _P),
+    ]
+
 # name -> (restype, argtypes); exactly the symbols include/ipp_engine.h declares
 PROTOTYPES = {
     "ipp_abi_version": (C.c_int, []),
@@ -205,6 +217,10 @@ PROTOTYPES = {
                                       _P, _P, _P]),
     "ipp_replay_gather_rows": (C.c_int, [C.POINTER(IppSelfPlay), C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ipp_replay_priority_update": (C.c_int, [C.POINTER(IppSelfPlay), _P, _P, _P, C.c_int32, _P]),
+    # (the deployment planner's and the arena's calls, csrc/k_play.h: added without an ABI bump, nothing existing changes layout)
+    "ipp_play_pick": (C.c_int, [C.POINTER(IppPlay), _P, _P, _P, _P]),
+    "ipp_play_tally": (C.c_int, [C.POINTER(IppPlay), _P]),
+    "ipp_play_totals": (C.c_int, [C.POINTER(IppPlay), _P, _P]),
     # (ops: an array of ipp_pvnet_op, planning/mcts_zero/networks.py IppPvnetOp)
     "ipp_pvnet_create": (C.c_int, [_P, C.c_int32, _P, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P)]),
     "ipp_pvnet_set_weights": (C.c_int, [_P, _P, C.c_uint64, _P]),

@@ -33,6 +33,7 @@
 #include "k_mcts.h"
 #include "k_selfplay.h"
 #include "k_replay_per.h"
+#include "k_play.h"
 #include "k_prepare.h"
 #include "patch_launch.h"
 
@@ -1873,6 +1874,51 @@ int ipp_replay_priority_update(const ipp_selfplay* sp, double* priority, const i
     HIP_TRY(hipSetDevice(sp->device));
     hipLaunchKernelGGL(k_per_update, dim3((unsigned)((n + kPerThreads - 1) / kPerThreads)), dim3(kPerThreads), 0,
                        reinterpret_cast<hipStream_t>(stream), (long long)sp->num_envs * sp->slots, (int)n, index, value, priority);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+namespace {
+int play_check(const ipp_play* pl) {
+    if (!pl) return fail(-1, "null argument");
+    if (pl->num_envs <= 0) return fail(-1, "ipp_play: num_envs = %d, need > 0", pl->num_envs);
+    if (pl->workers < 1 || (long long)pl->num_envs * pl->workers > INT32_MAX)
+        return fail(-1, "ipp_play: workers = %d, need >= 1 and num_envs x workers < 2^31", pl->workers);
+    if (pl->kmax < 1 || pl->kmax > kSpMaxK) return fail(-1, "ipp_play: kmax = %d outside [1, %d]", pl->kmax, kSpMaxK);
+    if (pl->num_actions <= 0) return fail(-1, "ipp_play: num_actions = %d", pl->num_actions);
+    if (pl->games_per_env < 1 || (long long)pl->num_envs * pl->games_per_env > INT32_MAX)
+        return fail(-1, "ipp_play: games_per_env = %d, need >= 1 and num_envs x games_per_env < 2^31", pl->games_per_env);
+    if (pl->tie_rule != 0 && pl->tie_rule != 1) return fail(-1, "ipp_play: tie_rule = %d, need 0 (deploy) or 1 (arena)", pl->tie_rule);
+    if (!pl->actions || !pl->budget || !pl->depth || !pl->episode || !pl->done || !pl->prev || !pl->reward || !pl->ret || !pl->steps ||
+        !pl->games || !pl->forced || !pl->tie_u || !pl->action || !pl->action_idx || !pl->game_value || !pl->game_steps)
+        return fail(-1, "ipp_play: null device pointer");
+    return 0;
+}
+}  // namespace
+
+int ipp_play_pick(const ipp_play* pl, const double* policy, const int32_t* valid_idx, const int32_t* ok, void* stream) {
+    if (int rc = play_check(pl)) return rc;
+    if (!policy || !valid_idx || !ok) return fail(-1, "null argument");
+    HIP_TRY(hipSetDevice(pl->device));
+    const size_t lds = (size_t)pl->kmax * (sizeof(double) + sizeof(int32_t));
+    hipLaunchKernelGGL(k_play_pick, dim3(pl->num_envs), dim3(kWave), lds, reinterpret_cast<hipStream_t>(stream), *pl, policy, valid_idx, ok);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ipp_play_tally(const ipp_play* pl, void* stream) {
+    if (int rc = play_check(pl)) return rc;
+    HIP_TRY(hipSetDevice(pl->device));
+    hipLaunchKernelGGL(k_play_tally, dim3(pl->num_envs), dim3(kWave), 0, reinterpret_cast<hipStream_t>(stream), *pl);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ipp_play_totals(const ipp_play* pl, double* out, void* stream) {
+    if (int rc = play_check(pl)) return rc;
+    if (!out) return fail(-1, "null argument");
+    HIP_TRY(hipSetDevice(pl->device));
+    hipLaunchKernelGGL(k_play_totals, dim3(1), dim3(kWave), 0, reinterpret_cast<hipStream_t>(stream), *pl, out);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -30,6 +30,9 @@ __device__ __forceinline__ double sp_uniform(uint64_t q, uint64_t subseq, uint64
 // counter of the per-step draws of an env: (global env id, depth in the episode); the episode is the subsequence offset
 __device__ __forceinline__ uint64_t sp_step_counter(long long gid, int depth) { return ((uint64_t)gid << 20) + (uint64_t)depth; }
 
+// gamma^j of the discounted sums (episode_generators.py:158, :163; arenas.py:38): one convention for the value targets and the arena's returns
+__device__ __forceinline__ double sp_discount(double gamma, int j) { return pow(gamma, (double)j); }
+
 // an env's step without a sample (no policy, or none with mass): a zero budget ends the episode inside the step launch (a reset exactly
 // like a budget end), the action is the current waypoint (no cost).  The row's planes were overwritten for this step: it is no longer
 // a committed sample; its earlier policy and valid set stay as they were.
@@ -163,14 +166,14 @@ __global__ __launch_bounds__(64) void k_sp_commit(ipp_selfplay sp, long long ste
         for (int i = lane; i < T; i += 64) {
             const int hi = min(i + sp.horizon, T);
             double v = 0.0;
-            for (int j = i; j < hi; ++j) v += pow(sp.gamma, (double)j) * r_of(j);
+            for (int j = i; j < hi; ++j) v += sp_discount(sp.gamma, j) * r_of(j);
             const size_t r = row_of(i);
             sp.r_value[r] = sqrt(1.0 + v) - 1.0;  // scale_value_target (planning/common/rewards.py)
             sp.r_flags[r] = kSpCommitted;          // (behind its target: a row becomes sampleable with its value written)
         }
         if (lane == 0) {
             double tot = 0.0;  // total_episode_value (:158)
-            for (int j = 0; j < T; ++j) tot += pow(sp.gamma, (double)j) * r_of(j);
+            for (int j = 0; j < T; ++j) tot += sp_discount(sp.gamma, j) * r_of(j);
             sp.episode_value[e] = tot;
             sp.ep_len[e] = 0;
             if (sp.random_init) {  // the episode the step's reset started: its first waypoint, uniform over the action set

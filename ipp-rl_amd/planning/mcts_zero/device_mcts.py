@@ -370,12 +370,14 @@ class DeviceMCTS(VectorMCTS):
         return [p for o in outs for p in o]
 
     def search_device(self, roots, previous_actions, budgets, temperatures: Sequence[float], tie_uniform, depth: int = 0,
-                      root_history=None):
+                      root_history=None, deploy_time: bool = False):
         """One search per root and the read-out ON THE DEVICE (ipp_mcts_policy) at each temperature > 0 of `temperatures`, whatever the
         number of actions: the self-play loop's search (selfplay.py).  roots: device int32 tensor of env slots; previous_actions [R, 3] and
         budgets [R]: device tensors -- nothing is copied from the host, so the waves' count read-backs are the only synchronisations.
         tie_uniform: device float64 [R], the uniform that keeps one of the most visited actions in the forced-playout take-back
-        (mcts.py:100).  Returns {"policy": [one [R, kmax] float64 tensor per temperature], "valid_idx": [R, kmax], "ok": [R]} (device
+        (mcts.py:100).  deploy_time=True: the deployment read-out (mcts.py:99: the visit counts as they are, the forced-playout take-back
+        of :100-128 is skipped; planning/vec_mcts_zero.py).  roots may name an env slot several times (root-parallel workers: the kernels only read the
+        slot).  Returns {"policy": [one [R, kmax] float64 tensor per temperature], "valid_idx": [R, kmax], "ok": [R]} (device
         tensors, valid until the next search)."""
         import torch
 
@@ -387,7 +389,7 @@ class DeviceMCTS(VectorMCTS):
         G = min(self.groups, R // 2)
         if G > 1 and self.queue_ahead and bool(int(self.engine.info.patch_layout)) and self.engine.max_batch >= R * self.sims_in_flight:
             outs = self._run_groups(G, roots, previous_actions, budgets, depth,
-                                    lambda sub, state, lo, n: sub._readout_device(state["b"], n, temps, tie_uniform[lo:lo + n]))
+                                    lambda sub, state, lo, n: sub._readout_device(state["b"], n, temps, tie_uniform[lo:lo + n], deploy_time))
             return {"policy": [torch.cat([o["policy"][i] for o in outs]) for i in range(len(temps))],
                     "valid_idx": torch.cat([o["valid_idx"] for o in outs]), "ok": torch.cat([o["ok"] for o in outs])}
         self._subs_used = None
@@ -397,9 +399,9 @@ class DeviceMCTS(VectorMCTS):
         self._host_rows = {}
         self._rows_src = (state["b"], R, self.nodes_per_root)
         self.root_ids = np.arange(R)
-        return self._readout_device(state["b"], R, temps, tie_uniform)
+        return self._readout_device(state["b"], R, temps, tie_uniform, deploy_time)
 
-    def _readout_device(self, b, R, temps, tie_uniform):
+    def _readout_device(self, b, R, temps, tie_uniform, deploy_time: bool = False):
         """ipp_mcts_policy of this table set at each temperature (one output buffer per temperature), with the caller's tie uniforms."""
         import torch
 
@@ -410,7 +412,8 @@ class DeviceMCTS(VectorMCTS):
         u = tie_uniform.to(torch.float64).contiguous()
         self._keep_tie = u
         for T, pol in zip(temps, pols):
-            _ffi.check(self.engine._lib.ipp_mcts_policy(C.byref(self._tab), u.data_ptr(), float(T), 0, pol.data_ptr(), o["valid_idx"].data_ptr(),
+            _ffi.check(self.engine._lib.ipp_mcts_policy(C.byref(self._tab), u.data_ptr(), float(T), int(bool(deploy_time)), pol.data_ptr(),
+                                                        o["valid_idx"].data_ptr(),
                                                         o["ok"].data_ptr(), self.engine.stream))
         self._rows_src = (b, R, self.nodes_per_root)
         self._host_rows = {}

@@ -1082,6 +1082,85 @@ int ipp_cma_objective(const float* reward, const int32_t* status, const double* 
 int ipp_cma_tell(void* state, int32_t n, int32_t nmax, int32_t lam, const float* normals, const double* x, const double* f, const double* scale,
                  int32_t device, void* stream);
 
+/*
+ * Reward of k candidate actions from the state of EACH of n tree nodes, in one call (csrc/k_rollout.h): the counterpart of
+ * ipp_score_actions_envs for search nodes -- per (node, candidate) exactly the reward of a predict-only ipp_tree_step from
+ * (root_ids[i], path_ids[i]) for that action; nothing is written to any env slot or node.  The call builds the item lists on the
+ * device and runs the predict-only tree-step launches itself, max_batch items at a time: n x k is not bound by max_batch.
+ * A "no candidate" row is NOT compacted away: it becomes an item whose non-finite action ends it in the step kernel's header before
+ * any address is formed from it (csrc/k_prepare.h make_item_header, csrc/k_tree_patch.h m == 0), which leaves reward 0 and
+ * IPP_STATUS_BAD_FOOTPRINT; its cost is NaN.
+ * Engines: those ipp_tree_step runs on (IPP_FACTOR with window_rows > 0, default tile_threads, node_capacity > 0: the patch layout
+ * and, on grids too small for it, the band-tile windowed kernels -- both end a non-finite action in make_item_header); every other
+ * engine returns an error.
+ *   root_ids    [dev]  int32[n]; repeats are allowed
+ *   path_ids    [dev]  int32[n][IPP_TREE_DEPTH] (root side first, -1 = unused)
+ *   actions     [dev]  double[n][k][3]; a row with a non-finite entry = no candidate
+ *   prev_action [dev]  double[n][3]      the waypoint of node i (the candidates' start)
+ *   flags              IPP_ADAPTIVE | IPP_USE_FLIGHT_TIME
+ *   reward      [dev]  float[n][k]
+ *   cost        [dev]  double[n][k] or NULL: the action cost (planning/common/actions.py:8-41), evaluated without fused multiply-adds
+ *   status      [dev]  int32[n][k] or NULL
+ *   scratch     [dev]  caller-owned, at least ipp_tree_score_nodes_scratch_bytes(engine, n, k) bytes: per candidate its root id,
+ *                      its path and its start waypoint (52 bytes)
+ */
+int ipp_tree_score_nodes(void* engine, const int32_t* root_ids, const int32_t* path_ids, int32_t n, int32_t k, const double* actions,
+                         const double* prev_action, uint32_t flags, float* reward, double* cost, int32_t* status, void* scratch,
+                         uint64_t scratch_bytes, void* stream);
+int ipp_tree_score_nodes_scratch_bytes(void* engine, int32_t n, int32_t k, uint64_t* bytes /*[host] out*/);
+
+/*
+ * Rollouts of the classic tree search on the device (csrc/k_rollout.h): n rollouts of the reference's MCTSMission.rollout /
+ * gcb_rollout (planning/mcts_mission.py:167-256) level by level -- candidates around the current waypoint, their rewards from the
+ * node's state, the eps-greedy or cost-benefit pick, one recorded tree step, the discounted return.  The caller owns every buffer
+ * ([dev] pointers) and supplies the uniforms, two per rollout and level: u[i][l][0] decides greedy / random (eps mode only),
+ * u[i][l][1] picks among the available candidates.  A rollout that ends keeps `value`, clears `live` and says why in `flag`.
+ * Candidate j of a rollout = cell offset j / n_levels of the (2 half + 1)^2 square around the current cell (row-major: row offset,
+ * then column offset) at altitude level j % n_levels; kmax = (2 half + 1)^2 n_levels.
+ */
+#define IPP_ROLLOUT_RUNNING       0 /* flag of a live rollout */
+#define IPP_ROLLOUT_END           1 /* depth_left == 0 or budget < resolution: the reference's return 0 */
+#define IPP_ROLLOUT_NO_ACTION     2 /* no available candidate where the reference calls np.random.choice(0): ends, adds no further value */
+#define IPP_ROLLOUT_RANK_FULL     3 /* the recorded step returned IPP_STATUS_RANK_FULL: its reward counts, the rollout ends */
+#define IPP_ROLLOUT_ERR_FOOTPRINT 4 /* error: an available candidate was scored IPP_STATUS_BAD_FOOTPRINT */
+#define IPP_ROLLOUT_ERR_NAN       5 /* error: no comparable reward (greedy: all NaN; cost-benefit: a NaN among them) */
+#define IPP_ROLLOUT_ERR_STEP      6 /* error: the recorded step returned a status other than OK / RANK_FULL */
+typedef struct ipp_rollout {
+    int32_t n;                /* rollouts */
+    int32_t kmax;             /* candidates per rollout and level */
+    int32_t max_depth;        /* levels issued by ipp_rollout_run; second dimension of u and pick_idx */
+    int32_t gcb;              /* 0 = eps-greedy rollout policy, 1 = generalised cost-benefit */
+    int32_t grid_w, grid_h;   /* cells along x / y */
+    int32_t n_levels, half;   /* altitude levels; half-width of the candidate square in cells = ceil(radius / resolution) */
+    int32_t node_base;        /* rollout i records level l as node node_base + i max_depth + l of the engine's node pool */
+    int32_t device;
+    uint32_t flags;           /* IPP_ADAPTIVE | IPP_USE_FLIGHT_TIME of the score and step launches */
+    int32_t reserved;
+    double resolution, radius, gamma, epsilon, vmax, amax;
+    const double* levels;     /* [n_levels] altitudes */
+    const double* u;          /* [n][max_depth][2] uniforms in [0, 1) */
+    /* per-rollout state */
+    int32_t* root; int32_t* path; int32_t* plen;   /* [n], [n][IPP_TREE_DEPTH] (-1 padded), [n]: the node the rollout has reached */
+    double* cur; double* charge_from;              /* [n][3] waypoint of that node; waypoint the next cost is charged from */
+    double* budget; int32_t* depth_left;           /* [n] */
+    double* value; double* disc;                   /* [n] discounted return so far, current discount */
+    int32_t* live; int32_t* flag;                  /* [n] */
+    /* working buffers */
+    double* cand; float* reward; double* cost; int32_t* status;   /* [n][kmax][3], [n][kmax] x 3 */
+    double* action; int32_t* new_id;               /* [n][3] picked waypoint (NaN: none), [n] node id of the recorded step (-1: none) */
+    float* step_reward; int32_t* step_status;      /* [n] of the recorded step */
+    int32_t* pick_idx;                             /* [n][max_depth] chosen candidate per level, untouched where nothing was picked */
+} ipp_rollout;
+/* cand of every rollout from cur; a rollout that is not live gets NaN rows */
+int ipp_rollout_candidates(const ipp_rollout* ro, void* stream);
+/* the decision of level `level` from cand / reward / cost / status: action, new_id, pick_idx; may end the rollout */
+int ipp_rollout_pick(const ipp_rollout* ro, int32_t level, void* stream);
+/* the recorded step's step_reward / step_status into value, disc, budget (charged from charge_from), cur, path, depth_left */
+int ipp_rollout_advance(const ipp_rollout* ro, void* stream);
+/* max_depth levels of {candidates, ipp_tree_score_nodes, pick, recording ipp_tree_step, advance} with no host read between them;
+ * scratch: ipp_tree_score_nodes_scratch_bytes(engine, n, kmax) bytes */
+int ipp_rollout_run(void* engine, const ipp_rollout* ro, void* scratch, uint64_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

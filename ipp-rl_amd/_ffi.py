@@ -134,6 +134,25 @@ class IppPlay(C.Structure):
         ("game_value", _P), ("game_steps", _P), ("ensemble", _P),
     ]
 
+class IppRollout(C.Structure):
+    """ipp_rollout (include/ipp_engine.h): dimensions, policy constants and the [dev] buffers of n device rollouts."""
+    _fields_ = [
+        ("n", C.c_int32), ("kmax", C.c_int32), ("max_depth", C.c_int32), ("gcb", C.c_int32),
+        ("grid_w", C.c_int32), ("grid_h", C.c_int32), ("n_levels", C.c_int32), ("half", C.c_int32),
+        ("node_base", C.c_int32), ("device", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_int32),
+        ("resolution", C.c_double), ("radius", C.c_double), ("gamma", C.c_double), ("epsilon", C.c_double),
+        ("vmax", C.c_double), ("amax", C.c_double),
+        ("levels", _P), ("u", _P),
+        ("root", _P), ("path", _P), ("plen", _P), ("cur", _P), ("charge_from", _P), ("budget", _P), ("depth_left", _P),
+        ("value", _P), ("disc", _P), ("live", _P), ("flag", _P),
+        ("cand", _P), ("reward", _P), ("cost", _P), ("status", _P), ("action", _P), ("new_id", _P),
+        ("step_reward", _P), ("step_status", _P), ("pick_idx", _P),
+    ]
+
+
+IPP_ROLLOUT_RUNNING, IPP_ROLLOUT_END, IPP_ROLLOUT_NO_ACTION, IPP_ROLLOUT_RANK_FULL = 0, 1, 2, 3
+IPP_ROLLOUT_ERR_FOOTPRINT, IPP_ROLLOUT_ERR_NAN, IPP_ROLLOUT_ERR_STEP = 4, 5, 6
+
 # name -> (restype, argtypes); exactly the symbols include/ipp_engine.h declares
 PROTOTYPES = {
     "ipp_abi_version": (C.c_int, []),
@@ -239,6 +258,13 @@ PROTOTYPES = {
                                C.c_int32, C.c_double, C.c_double, _P, _P, _P, _P, _P, C.c_int32, _P]),
     "ipp_cma_objective": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
     "ipp_cma_tell": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, _P]),
+    # (classic MCTS for a batch, csrc/k_rollout.h: added without an ABI bump as well)
+    "ipp_tree_score_nodes": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P, C.c_uint32, _P, _P, _P, _P, C.c_uint64, _P]),
+    "ipp_tree_score_nodes_scratch_bytes": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]),
+    "ipp_rollout_candidates": (C.c_int, [C.POINTER(IppRollout), _P]),
+    "ipp_rollout_pick": (C.c_int, [C.POINTER(IppRollout), C.c_int32, _P]),
+    "ipp_rollout_advance": (C.c_int, [C.POINTER(IppRollout), _P]),
+    "ipp_rollout_run": (C.c_int, [_P, C.POINTER(IppRollout), _P, C.c_uint64, _P]),
 }
 
 _lib = None

@@ -34,6 +34,7 @@
 #include "k_selfplay.h"
 #include "k_replay_per.h"
 #include "k_play.h"
+#include "k_rollout.h"
 #include "k_prepare.h"
 #include "patch_launch.h"
 
@@ -2303,6 +2304,127 @@ int ipp_profile_read_busy(void* engine, int32_t kind, double* busy_ms, int64_t* 
     if (busy_ms) *busy_ms = p.busy_ms;
     if (launches) *launches = p.busy_launches;
     if (reset) { p.busy_ms = 0.0; p.busy_launches = 0; }
+    return 0;
+}
+
+// ---- classic MCTS for a batch (k_rollout.h): candidate scoring from many tree nodes, the rollout policy on the device
+static const char* kNodesEngineMsg = "ipp_tree_score_nodes and ipp_rollout_run need an engine ipp_tree_step runs on: IPP_FACTOR with window_rows > 0, the default tile_threads and node_capacity > 0";
+
+int ipp_tree_score_nodes_scratch_bytes(void* engine, int32_t n, int32_t k, uint64_t* bytes) {
+    Engine* e = as_engine(engine);
+    if (!e || !bytes) return fail(-1, "null argument");
+    if (n < 0 || k < 0) return fail(-1, "n = %d, k = %d: negative", n, k);
+    if (!e->tree_ok || e->tv.node_cap <= 0) return fail(-1, "%s", kNodesEngineMsg);
+    *bytes = nodes_scratch_bytes((uint64_t)n * (uint64_t)k);
+    return 0;
+}
+
+int ipp_tree_score_nodes(void* engine, const int32_t* root_ids, const int32_t* path_ids, int32_t n, int32_t k, const double* actions,
+                         const double* prev_action, uint32_t flags, float* reward, double* cost, int32_t* status, void* scratch,
+                         uint64_t scratch_bytes, void* stream) {
+    Engine* e = as_engine(engine);
+    if (!e || !root_ids || !path_ids || !actions || !prev_action || !reward) return fail(-1, "null argument");
+    if (!e->tree_ok || e->tv.node_cap <= 0) return fail(-1, "%s", kNodesEngineMsg);
+    if (n < 0 || k < 0) return fail(-1, "n = %d, k = %d: negative", n, k);
+    if (flags & ~(IPP_ADAPTIVE | IPP_USE_FLIGHT_TIME)) return fail(-1, "unsupported flag bits 0x%x", flags);
+    const uint64_t items = (uint64_t)n * (uint64_t)k;
+    const uint64_t need = nodes_scratch_bytes(items);
+    if (items == 0) return 0;
+    if (scratch_bytes < need || !scratch)
+        return fail(-1, "scratch of %llu bytes, ipp_tree_score_nodes needs %llu for n = %d, k = %d", (unsigned long long)scratch_bytes,
+                    (unsigned long long)need, n, k);
+    if ((items + 255) / 256 > 0x7fffffffull) return fail(-1, "n x k = %llu candidates exceed one call", (unsigned long long)items);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(e->device));
+    unsigned char* base = reinterpret_cast<unsigned char*>(scratch);
+    int* roots = reinterpret_cast<int*>(base);
+    int* paths = reinterpret_cast<int*>(base + nodes_scratch_align(items * 4));
+    double* prevx = reinterpret_cast<double*>(base + nodes_scratch_align(items * 4) + nodes_scratch_align(items * 4 * kTreeDepth));
+    hipLaunchKernelGGL(k_nodes_expand, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, n, k, root_ids, path_ids, actions, prev_action,
+                       flags, e->v.vmax, e->v.amax, roots, paths, prevx, cost);
+    HIP_TRY(hipGetLastError());
+    // one predict-only item per candidate, in launches of at most max_batch items: the candidates of a node are consecutive items
+    const uint32_t step_flags = (flags & (IPP_ADAPTIVE | IPP_USE_FLIGHT_TIME)) | IPP_PREDICT_ONLY;
+    const uint64_t mb = (uint64_t)e->v.max_batch;
+    for (uint64_t o = 0; o < items; o += mb) {
+        const int cnt = (int)std::min<uint64_t>(mb, items - o);
+        if (int rc = tree_step_impl(engine, roots + o, paths + kTreeDepth * o, nullptr, cnt, actions + 3 * o, prevx + 3 * o, step_flags,
+                                    reward + o, status ? status + o : nullptr, stream, nullptr))
+            return rc;
+    }
+    return 0;
+}
+
+static int rollout_check(const ipp_rollout* ro) {
+    if (!ro) return fail(-1, "null rollout");
+    if (ro->n <= 0 || ro->kmax <= 0 || ro->max_depth <= 0 || ro->n_levels <= 0 || ro->half < 0 || ro->grid_w <= 0 || ro->grid_h <= 0)
+        return fail(-1, "ipp_rollout: n, kmax, max_depth, n_levels, grid_w and grid_h must be positive, half >= 0");
+    if ((int64_t)(2 * ro->half + 1) * (2 * ro->half + 1) * ro->n_levels != (int64_t)ro->kmax)
+        return fail(-1, "ipp_rollout.kmax = %d is not (2 half + 1)^2 n_levels = (2 x %d + 1)^2 x %d", ro->kmax, ro->half, ro->n_levels);
+    if (ro->max_depth > kTreeDepth) return fail(-1, "ipp_rollout.max_depth = %d exceeds IPP_TREE_DEPTH", ro->max_depth);
+    if ((int64_t)ro->n * ro->max_depth > 0x7fffffffll - (int64_t)std::max(ro->node_base, 0) || ro->node_base < 0)
+        return fail(-1, "ipp_rollout.node_base = %d with n max_depth = %lld node ids", ro->node_base, (long long)ro->n * ro->max_depth);
+    if (ro->gcb != 0 && ro->gcb != 1) return fail(-1, "ipp_rollout.gcb = %d is neither 0 nor 1", ro->gcb);
+    if ((size_t)ro->kmax * sizeof(double) > 48 * 1024) return fail(-1, "ipp_rollout.kmax = %d exceeds the pick kernel's LDS row", ro->kmax);
+    if (!ro->levels || !ro->u || !ro->root || !ro->path || !ro->plen || !ro->cur || !ro->charge_from || !ro->budget || !ro->depth_left ||
+        !ro->value || !ro->disc || !ro->live || !ro->flag || !ro->cand || !ro->reward || !ro->cost || !ro->status || !ro->action ||
+        !ro->new_id || !ro->step_reward || !ro->step_status || !ro->pick_idx)
+        return fail(-1, "ipp_rollout: null buffer");
+    return 0;
+}
+
+int ipp_rollout_candidates(const ipp_rollout* ro, void* stream) {
+    if (int rc = rollout_check(ro)) return rc;
+    HIP_TRY(hipSetDevice(ro->device));
+    const uint64_t items = (uint64_t)ro->n * (uint64_t)ro->kmax;
+    hipLaunchKernelGGL(k_rollout_candidates, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *ro);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ipp_rollout_pick(const ipp_rollout* ro, int32_t level, void* stream) {
+    if (int rc = rollout_check(ro)) return rc;
+    if (level < 0 || level >= ro->max_depth) return fail(-1, "level = %d outside [0, max_depth = %d)", level, ro->max_depth);
+    HIP_TRY(hipSetDevice(ro->device));
+    hipLaunchKernelGGL(k_rollout_pick, dim3(ro->n), dim3(kWave), (size_t)ro->kmax * sizeof(double), reinterpret_cast<hipStream_t>(stream), *ro,
+                       level);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ipp_rollout_advance(const ipp_rollout* ro, void* stream) {
+    if (int rc = rollout_check(ro)) return rc;
+    HIP_TRY(hipSetDevice(ro->device));
+    hipLaunchKernelGGL(k_rollout_advance, dim3((ro->n + kWave - 1) / kWave), dim3(kWave), 0, reinterpret_cast<hipStream_t>(stream), *ro);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ipp_rollout_run(void* engine, const ipp_rollout* ro, void* scratch, uint64_t scratch_bytes, void* stream) {
+    Engine* e = as_engine(engine);
+    if (!e) return fail(-1, "null engine");
+    if (int rc = rollout_check(ro)) return rc;
+    if (!e->tree_ok || e->tv.node_cap <= 0) return fail(-1, "%s", kNodesEngineMsg);
+    if ((int64_t)ro->node_base + (int64_t)ro->n * ro->max_depth > (int64_t)e->tv.node_cap)
+        return fail(-1, "rollout nodes [%d, %lld) exceed node_capacity = %d", ro->node_base, (long long)ro->node_base + (long long)ro->n * ro->max_depth,
+                    e->tv.node_cap);
+    if (ro->device != e->device) return fail(-1, "ipp_rollout.device = %d, the engine runs on %d", ro->device, e->device);
+    if (ro->flags & ~(uint32_t)(IPP_ADAPTIVE | IPP_USE_FLIGHT_TIME)) return fail(-1, "unsupported flag bits 0x%x", ro->flags);
+    const int mb = e->v.max_batch;
+    for (int l = 0; l < ro->max_depth; ++l) {
+        if (int rc = ipp_rollout_candidates(ro, stream)) return rc;
+        if (int rc = ipp_tree_score_nodes(engine, ro->root, ro->path, ro->n, ro->kmax, ro->cand, ro->cur, ro->flags, ro->reward, ro->cost, ro->status,
+                                          scratch, scratch_bytes, stream))
+            return rc;
+        if (int rc = ipp_rollout_pick(ro, l, stream)) return rc;
+        for (int o = 0; o < ro->n; o += mb) {  // the recorded step of every rollout (a NaN action: nothing is applied)
+            const int cnt = std::min(mb, ro->n - o);
+            if (int rc = tree_step_impl(engine, ro->root + o, ro->path + (size_t)kTreeDepth * o, ro->new_id + o, cnt, ro->action + 3 * (size_t)o,
+                                        ro->cur + 3 * (size_t)o, ro->flags, ro->step_reward + o, ro->step_status + o, stream, nullptr))
+                return rc;
+        }
+        if (int rc = ipp_rollout_advance(ro, stream)) return rc;
+    }
     return 0;
 }
 

@@ -459,6 +459,38 @@ class IPPEngine:
         self._keep = (roots, paths, new, a, p)
         return reward, status
 
+    def tree_score_nodes(self, root_ids, path_ids, actions, prev, *, adaptive=True, use_flight_time=True, want_cost=False):
+        """Reward of k candidate actions from the state of each of n tree nodes in one call (ipp_tree_score_nodes; patch-layout engines
+        with node_capacity > 0): root_ids [n], path_ids [n, TREE_DEPTH] (-1 padded), actions [n, k, 3] (a NaN row = no candidate),
+        prev [n, 3] the nodes' waypoints.  Returns (reward [n, k] float32, status [n, k] int32[, cost [n, k] float64]); nothing is
+        written to any env or node and nothing is read back to the host.  One scratch tensor per (n, k) shape stays alive between calls."""
+        torch = _torch()
+        a = self._dev(actions, torch.float64)
+        if a.dim() != 3 or a.shape[2] != 3:
+            raise ValueError("actions must be [n, k, 3]")
+        n, k = int(a.shape[0]), int(a.shape[1])
+        a = a.contiguous()
+        p = self._dev(prev, torch.float64).reshape(-1, 3).contiguous()
+        roots = self._dev(root_ids, torch.int32).reshape(-1).contiguous()
+        paths = self._dev(path_ids, torch.int32).reshape(-1, self.TREE_DEPTH).contiguous()
+        if p.shape[0] != n or roots.numel() != n or paths.shape[0] != n:
+            raise ValueError("root_ids, path_ids and prev need one row per row of actions")
+        cache = self.__dict__.setdefault("_score_nodes_scratch", {})
+        scratch = cache.get((n, k))
+        if scratch is None:
+            nbytes = C.c_uint64(0)
+            _ffi.check(self._lib.ipp_tree_score_nodes_scratch_bytes(self._h, n, k, C.byref(nbytes)))
+            scratch = cache[(n, k)] = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
+        reward = torch.empty((n, k), dtype=torch.float32, device=self.device)
+        status = torch.empty((n, k), dtype=torch.int32, device=self.device)
+        cost = torch.empty((n, k), dtype=torch.float64, device=self.device) if want_cost else None
+        flags = (_ffi.IPP_ADAPTIVE if adaptive else 0) | (_ffi.IPP_USE_FLIGHT_TIME if use_flight_time else 0)
+        _ffi.check(self._lib.ipp_tree_score_nodes(self._h, self._ptr(roots), self._ptr(paths), n, k, self._ptr(a), self._ptr(p), flags,
+                                                  self._ptr(reward), self._ptr(cost), self._ptr(status),
+                                                  self._ptr(scratch) if scratch.numel() else None, int(scratch.numel()), self.stream))
+        self._keep_score = (a, p, roots, paths)
+        return (reward, status, cost) if want_cost else (reward, status)
+
     def tree_score_actions(self, root: int, path, actions, prev_action, *, adaptive=True, use_flight_time=True):
         """score_actions from the state of a tree node (root env slot + node path, host list padded with -1)."""
         torch = _torch()

@@ -28,6 +28,14 @@ two parameters).
 Randomness: every root owns a NumPy legacy generator (the reference's `np.random`, seeded `worker_id * 42 + 1` per worker,
 :314) and a `random.Random` (the reference's `random.choice` among UCT ties, :66); with the same seeds a root reproduces
 the reference's call sequence (tests/test_hip_mcts_mission.py against a recorded search of the imported reference).
+
+batched=True (classic MCTS for a batch): a rollout is ONE request answered on the device (planning/device_rollout.py, csrc/k_rollout.h:
+candidates, scoring, pick, recorded step and return of every level without a host read), all rollouts pending in a round go into one
+DeviceRollout.run and all `score` requests of a round (expansions) into one ipp_tree_score_nodes call.  The tree itself (UCT,
+progressive widening, backup) stays on the host.  A rollout takes its uniforms from its root's own np_rng (random_sample((depth, 2))),
+so a root's search does not depend on the roots beside it -- but the stream is consumed differently from NumPy's randint-based choice:
+a batched search does not reproduce a search recorded from the reference.  A rollout that has no available action where the reference
+would raise in np.random.choice(0) ends there and adds no further value (IPP_ROLLOUT_NO_ACTION).
 """
 from __future__ import annotations
 
@@ -107,10 +115,13 @@ class ClassicMCTS:
                  altitude_spacing: float, num_simulations: int = 100, gamma: float = 0.95, c: float = 2.0,
                  episode_horizon: int = 5, k: float = 4.0, alpha: float = 0.75, epsilon_expand: float = 0.2,
                  epsilon_rollout: float = 0.5, max_greedy_radius: float = 3, use_gcb_rollout: bool = False, adaptive: bool = False,
-                 node_capacity: Optional[int] = None):
+                 node_capacity: Optional[int] = None, batched: bool = False):
         """engine: factor-state IPPEngine with window_rows > 0, score_scratch=True and node_capacity > 0 whose env slots hold
-        the roots (mean, covariance, ground truth); the other arguments are MCTSMission's (mcts_mission.py:69-165)."""
+        the roots (mean, covariance, ground truth); the other arguments are MCTSMission's (mcts_mission.py:69-165).
+        batched: rollouts and candidate scoring for all roots at once on the device (module docstring); the engine then needs no
+        score_scratch, and the last roots x episode_horizon nodes of the pool are the rollouts' scratch range."""
         self.engine, self.cfg, self.uav = engine, cfg, uav_specifications
+        self.batched = bool(batched)
         self.num_simulations, self.gamma, self.c = int(num_simulations), float(gamma), float(c)
         self.episode_horizon, self.k, self.alpha = int(episode_horizon), float(k), float(alpha)
         self.epsilon_expand, self.epsilon_rollout = float(epsilon_expand), float(epsilon_rollout)
@@ -125,6 +136,11 @@ class ClassicMCTS:
         if uav_specifications is not None:
             engine.set_uav(uav_specifications["max_v"], uav_specifications["max_a"])
         self.stats = dict(device_steps=0, launches=0, score_calls=0)
+        if self.batched:
+            self.stats.update(rounds=0, rollout_calls=0, rollouts=0, scored_nodes=0)
+            self.min_altitude, self.max_altitude, self.altitude_spacing = float(min_altitude), float(max_altitude), float(altitude_spacing)
+            self.max_greedy_radius = float(max_greedy_radius)
+            self._device_rollouts = {}
 
     # ------------------------------------------------------------------ policies (generators: `yield` = a device request)
     def _mask(self, node: Node, remaining_budget: float) -> np.ndarray:
@@ -158,6 +174,8 @@ class ClassicMCTS:
         """rollout / gcb_rollout (:175-200, :223-239); the nodes it creates are not attached to the tree."""
         if depth == 0 or remaining_budget < self.resolution:
             return 0
+        if self.batched:  # (previous_action is node.action at the top of a rollout, :280-282: the device starts charging from there)
+            return (yield ("rollout", node, remaining_budget, depth))
         if self.use_gcb_rollout:
             action = yield from self._gcb(s, node, remaining_budget)
         else:
@@ -202,6 +220,7 @@ class ClassicMCTS:
         """Walk every root's search to its end: the pending `step` requests of all roots go into ONE ipp_tree_step launch per
         round, `score` requests are answered one state at a time (ipp_tree_score_actions)."""
         n_sims = self.num_simulations if num_simulations is None else int(num_simulations)
+        rollout = self._rollout_scratch(len(searches), n_sims) if self.batched else None
         gens = [self._search(s, n_sims) for s in searches]
         pending, live = [None] * len(gens), []
         for i, g in enumerate(gens):
@@ -212,6 +231,10 @@ class ClassicMCTS:
                 pass
         while live:
             answers = {}
+            if self.batched:
+                self.stats["rounds"] += 1
+                self._answer_scores(pending, live, answers)
+                self._answer_rollouts(rollout, searches, pending, live, answers)
             steps = [i for i in live if pending[i][0] == "step"]
             if steps:
                 roots = [pending[i][1].root for i in steps]
@@ -232,7 +255,7 @@ class ClassicMCTS:
                     searches[i].nodes += 1
                     answers[i] = child
             for i in live:
-                if pending[i][0] == "score":
+                if pending[i][0] == "score" and not self.batched:
                     node, actions = pending[i][1], pending[i][2]
                     answers[i] = self.policy.score(node.root, node.path, node.action, actions)
                     self.stats["score_calls"] += 1
@@ -245,6 +268,69 @@ class ClassicMCTS:
                     pass
             live = still
         return [s.root for s in searches]
+
+    # ------------------------------------------------------------------ batched=True: one device call per kind of request and round
+    def _rollout_scratch(self, n_roots: int, n_sims: int):
+        """The DeviceRollout whose nodes are the last n_roots x episode_horizon ids of the pool; a simulation adds at most one tree
+        node, so the tree's nodes and the rollouts' must fit the pool together."""
+        from .device_rollout import DeviceRollout
+
+        base = self.pool.capacity - n_roots * self.episode_horizon
+        need = len(self.pool) + n_roots * n_sims
+        if base < need:
+            raise ValueError(f"node_capacity {self.pool.capacity} too small for a batched search: {n_roots} roots x {n_sims} simulations need "
+                             f"{need} tree nodes and {n_roots} x {self.episode_horizon} rollout nodes behind them")
+        ro = self._device_rollouts.get(base)
+        if ro is None:
+            ro = self._device_rollouts[base] = DeviceRollout(self.engine, self.min_altitude, self.max_altitude, self.altitude_spacing, self.uav,
+                                                             self.max_greedy_radius, self.gamma, self.epsilon_rollout, self.use_gcb_rollout,
+                                                             self.episode_horizon, base)
+        return ro
+
+    def _answer_scores(self, pending, live, answers) -> None:
+        """All `score` requests of a round in one ipp_tree_score_nodes call, padded with NaN rows to the widest candidate list."""
+        ask = [i for i in live if pending[i][0] == "score"]
+        if not ask:
+            return
+        k = max(len(pending[i][2]) for i in ask)
+        acts = np.full((len(ask), k, 3), np.nan)
+        for j, i in enumerate(ask):
+            acts[j, : len(pending[i][2])] = pending[i][2]
+        nodes = [pending[i][1] for i in ask]
+        paths = np.array([(n.path + [-1] * self.engine.TREE_DEPTH)[: self.engine.TREE_DEPTH] for n in nodes], dtype=np.int32)
+        reward, status = self.engine.tree_score_nodes([n.root for n in nodes], paths, acts, np.array([n.action for n in nodes]),
+                                                      adaptive=True, use_flight_time=self.uav is not None)
+        out = np.stack([reward.detach().cpu().numpy().astype(np.float64), status.detach().cpu().numpy().astype(np.float64)])  # (two reads)
+        self.stats["score_calls"] += 1
+        self.stats["scored_nodes"] += len(ask)
+        for j, i in enumerate(ask):
+            m = len(pending[i][2])
+            if np.any(out[1, j, :m] != 0):
+                raise ValueError("a candidate footprint was rejected by the engine")
+            answers[i] = out[0, j, :m]
+
+    def _answer_rollouts(self, rollout, searches, pending, live, answers) -> None:
+        """All `rollout` requests of a round in one DeviceRollout.run; one read brings the values and flags back."""
+        from . import device_rollout as dr
+
+        ask = [i for i in live if pending[i][0] == "rollout"]
+        if not ask:
+            return
+        nodes = [pending[i][1] for i in ask]
+        depths = [int(pending[i][3]) for i in ask]
+        u = np.zeros((len(ask), self.episode_horizon, 2))
+        for j, i in enumerate(ask):  # each root's own stream: the draw does not depend on which roots run beside it
+            u[j, : depths[j]] = searches[i].np_rng.random_sample((depths[j], 2))
+        values, flags = rollout.run([n.root for n in nodes], [n.path for n in nodes], np.array([n.action for n in nodes]),
+                                    [float(pending[i][2]) for i in ask], depths, u)
+        torch = rollout.torch
+        both = torch.stack([values, flags.to(torch.float64)]).cpu().numpy()  # the one read
+        self.stats["rollout_calls"] += 1
+        self.stats["rollouts"] += len(ask)
+        if np.isin(both[1], dr.ERROR_FLAGS).any():
+            raise ValueError(f"a device rollout ended with an error flag: {both[1].astype(int).tolist()}")
+        for j, i in enumerate(ask):
+            answers[i] = float(both[0, j])
 
     def new_search(self, root_slot: int, previous_action, budget: float, worker_id: int = 0, py_seed: Optional[int] = None) -> _Search:
         """A root with the reference's per-worker NumPy seed (run_simulations_proxy, :314)."""

@@ -1120,7 +1120,8 @@ int ipp_tree_score_nodes_scratch_bytes(void* engine, int32_t n, int32_t k, uint6
  */
 #define IPP_ROLLOUT_RUNNING       0 /* flag of a live rollout */
 #define IPP_ROLLOUT_END           1 /* depth_left == 0 or budget < resolution: the reference's return 0 */
-#define IPP_ROLLOUT_NO_ACTION     2 /* no available candidate where the reference calls np.random.choice(0): ends, adds no further value */
+#define IPP_ROLLOUT_NO_ACTION     2 /* no available candidate where the reference calls np.random.choice(0): ends, adds no further value
+                                     (on an EXPANSION of the device tree, ipp_ctree_attach below: no child, the node counts as terminal) */
 #define IPP_ROLLOUT_RANK_FULL     3 /* the recorded step returned IPP_STATUS_RANK_FULL: its reward counts, the rollout ends */
 #define IPP_ROLLOUT_ERR_FOOTPRINT 4 /* error: an available candidate was scored IPP_STATUS_BAD_FOOTPRINT */
 #define IPP_ROLLOUT_ERR_NAN       5 /* error: no comparable reward (greedy: all NaN; cost-benefit: a NaN among them) */
@@ -1160,6 +1161,76 @@ int ipp_rollout_advance(const ipp_rollout* ro, void* stream);
 /* max_depth levels of {candidates, ipp_tree_score_nodes, pick, recording ipp_tree_step, advance} with no host read between them;
  * scratch: ipp_tree_score_nodes_scratch_bytes(engine, n, kmax) bytes */
 int ipp_rollout_run(void* engine, const ipp_rollout* ro, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/*
+ * Classic MCTS for a batch with the tree on the device (csrc/k_ctree.h): UCT selection, progressive widening, attaching the expanded
+ * child, backup and best child of the reference's MCTSMission (planning/mcts_mission.py:24-66, :258-304, :341-351) in caller-owned
+ * tables, `roots` searches advancing one simulation at a time in lock step.  Per root `cap` node slots (cap = simulations + 1), slot 0
+ * is the root; a simulation adds at most one node and nodes are created in ascending slot order, so the children of a node are the
+ * slots with parent == node in ascending order.  The geometry (grid, candidate square, radius, altitude levels), the cost mode and
+ * `resolution` are those of the ipp_rollout structs passed beside the tables.
+ * Two ipp_rollout states travel with the tables: `rollout` (max_depth = horizon; a leaf's MCTSMission.rollout) and `expand`
+ * (max_depth = 1, gcb = 0, epsilon = epsilon_expand: the eps-greedy expansion policy); both with n = roots and the same kmax.  A row
+ * that a simulation does not use is left with live = 0.
+ * An expansion whose pick ends with IPP_ROLLOUT_NO_ACTION -- nothing reachable, where the reference and the host tree raise inside
+ * np.random.choice(0) -- makes no child: the simulation's value at that node is 0 and the node counts as the terminal case.
+ * err[i] != 0 ends root i's search: every kernel skips the root (descend still clears `live` of its two state rows).
+ */
+#define IPP_CTREE_TERMINAL 0 /* leaf kind: depth == 0 or budget < resolution at the last slot of the trace; value 0, the slot is not visited by itself */
+#define IPP_CTREE_ROLLOUT  1 /* the last slot of the trace was never visited: its row of `rollout` is live */
+#define IPP_CTREE_EXPAND   2 /* the last slot of the trace widens: its row of `expand` is live (between descend and attach only) */
+#define IPP_CTREE_ERR_RANGE   1 /* err: a count, slot, visit counter or path length read from a table is out of range */
+#define IPP_CTREE_ERR_SELECT  2 /* err: no child with a comparable UCT value */
+#define IPP_CTREE_ERR_PICK    3 /* err: the expansion's pick ended with an error flag (the flag in bits 8..) */
+#define IPP_CTREE_ERR_STEP    4 /* err: the expansion's recorded step returned a status other than OK (the status in bits 8..) */
+#define IPP_CTREE_ERR_FULL    5 /* err: no free node slot */
+#define IPP_CTREE_ERR_ROLLOUT 6 /* err: the leaf's rollout ended with an error flag (the flag in bits 8..) */
+typedef struct ipp_ctree {
+    int32_t roots;            /* searches = rows of the two ipp_rollout states */
+    int32_t cap;              /* node slots per root */
+    int32_t horizon;          /* episode_horizon: levels walked at most, depth of a rollout */
+    int32_t thr_len;          /* entries of thr; 2 simulations + 3 covers the double increments */
+    int32_t tree_node_base;   /* ipp_ctree_search: root i's node of simulation s is engine node tree_node_base + s roots + i */
+    int32_t device;
+    double c;                 /* UCT exploration constant */
+    const double* thr;        /* [thr_len] k v^alpha in fp64 from the host (pow on the device may differ in the last bit) */
+    const int32_t* root_slot; /* [roots] env slots */
+    const double* root_wp;    /* [roots][3] the roots' waypoints */
+    const double* root_budget;/* [roots] the roots' budgets */
+    const double* tie_u;      /* [roots][horizon] this simulation's tie uniforms, one per level; ipp_ctree_search: [sims][roots][horizon] */
+    /* per node: [roots][cap] */
+    int32_t* parent;          /* slot of the parent, -1 for the root */
+    int32_t* dev;             /* engine node id, -1 for the root env slot */
+    int32_t* plen; int32_t* path;   /* nodes on the path, [roots][cap][IPP_TREE_DEPTH] their ids (root side first, -1 padded) */
+    double* action;           /* [roots][cap][3] waypoint */
+    int32_t* visits;
+    double* value_sum;
+    double* edge_reward;      /* the recorded step's fp32 reward, widened */
+    /* per root */
+    int32_t* count;           /* [roots] slots in use */
+    int32_t* err;             /* [roots] 0 = fine */
+    int32_t* t_len; int32_t* t_slot;   /* this simulation's trace: [roots] slots visited, [roots][horizon + 1] the slots, root first */
+    int32_t* leaf_kind;       /* [roots] IPP_CTREE_TERMINAL / _ROLLOUT / _EXPAND */
+    double* leaf_budget; int32_t* leaf_depth;   /* [roots] budget and depth at the last slot of the trace */
+} ipp_ctree;
+/* one simulation's descent from slot 0 (budget root_budget, waypoint root_wp, depth horizon): trace, leaf kind, the leaf's row of
+ * `rollout` or `expand`; the other rows get live = 0 */
+int ipp_ctree_descend(const ipp_ctree* ct, const ipp_rollout* expand, const ipp_rollout* rollout, void* stream);
+/* after the expansion's candidates / score / pick(level 0) / recording step: the new child slot, then its terminal case or its rollout row */
+int ipp_ctree_attach(const ipp_ctree* ct, const ipp_rollout* expand, const ipp_rollout* rollout, void* stream);
+/* the leaf's rollout value (rollout->value) and the edge rewards up the trace */
+int ipp_ctree_backup(const ipp_ctree* ct, const ipp_rollout* rollout, void* stream);
+/* action [dev] double[roots][3], has [dev] int32[roots]: the first child of slot 0 with the largest value_sum / visits and 1, or the
+ * root's own waypoint and 0 when there is no child or err != 0 */
+int ipp_ctree_best(const ipp_ctree* ct, double* action, int32_t* has, void* stream);
+/* Simulations [first_sim, first_sim + n_sims) with no host read: per simulation s descend, ipp_rollout_candidates(expand),
+ * ipp_tree_score_nodes, ipp_rollout_pick(expand, 0), the recording tree step in max_batch chunks, attach, ipp_rollout_run(rollout),
+ * backup.  The two states are taken by value; per simulation expand.node_base = tree_node_base + s roots and the uniform pointers
+ * move to simulation s's block of the caller's tables: ct->tie_u [sims][roots][horizon], expand->u [sims][roots][1][2],
+ * rollout->u [sims][roots][horizon][2].  scratch: ipp_tree_score_nodes_scratch_bytes(engine, roots, kmax) bytes.  The tree nodes
+ * [tree_node_base, tree_node_base + (cap - 1) roots) and the rollout's nodes must lie in the engine's node pool and apart. */
+int ipp_ctree_search(void* engine, const ipp_ctree* ct, const ipp_rollout* expand, const ipp_rollout* rollout, void* scratch,
+                     uint64_t scratch_bytes, int32_t first_sim, int32_t n_sims, void* stream);
 
 #ifdef __cplusplus
 }

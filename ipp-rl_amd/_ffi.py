@@ -153,6 +153,21 @@ class IppRollout(C.Structure):
 IPP_ROLLOUT_RUNNING, IPP_ROLLOUT_END, IPP_ROLLOUT_NO_ACTION, IPP_ROLLOUT_RANK_FULL = 0, 1, 2, 3
 IPP_ROLLOUT_ERR_FOOTPRINT, IPP_ROLLOUT_ERR_NAN, IPP_ROLLOUT_ERR_STEP = 4, 5, 6
 
+
+class IppCtree(C.Structure):
+    """ipp_ctree (include/ipp_engine.h): dimensions, the UCT constant and the [dev] tables of a device-side classic tree search."""
+    _fields_ = [
+        ("roots", C.c_int32), ("cap", C.c_int32), ("horizon", C.c_int32), ("thr_len", C.c_int32),
+        ("tree_node_base", C.c_int32), ("device", C.c_int32), ("c", C.c_double),
+        ("thr", _P), ("root_slot", _P), ("root_wp", _P), ("root_budget", _P), ("tie_u", _P),
+        ("parent", _P), ("dev", _P), ("plen", _P), ("path", _P), ("action", _P), ("visits", _P), ("value_sum", _P), ("edge_reward", _P),
+        ("count", _P), ("err", _P), ("t_len", _P), ("t_slot", _P), ("leaf_kind", _P), ("leaf_budget", _P), ("leaf_depth", _P),
+    ]
+
+
+IPP_CTREE_TERMINAL, IPP_CTREE_ROLLOUT, IPP_CTREE_EXPAND = 0, 1, 2
+IPP_CTREE_ERR_RANGE, IPP_CTREE_ERR_SELECT, IPP_CTREE_ERR_PICK, IPP_CTREE_ERR_STEP, IPP_CTREE_ERR_FULL, IPP_CTREE_ERR_ROLLOUT = 1, 2, 3, 4, 5, 6
+
 # name -> (restype, argtypes); exactly the symbols include/ipp_engine.h declares
 PROTOTYPES = {
     "ipp_abi_version": (C.c_int, []),
@@ -265,6 +280,13 @@ PROTOTYPES = {
     "ipp_rollout_pick": (C.c_int, [C.POINTER(IppRollout), C.c_int32, _P]),
     "ipp_rollout_advance": (C.c_int, [C.POINTER(IppRollout), _P]),
     "ipp_rollout_run": (C.c_int, [_P, C.POINTER(IppRollout), _P, C.c_uint64, _P]),
+    # (the classic tree search's tables, csrc/k_ctree.h: added without an ABI bump as well)
+    "ipp_ctree_descend": (C.c_int, [C.POINTER(IppCtree), C.POINTER(IppRollout), C.POINTER(IppRollout), _P]),
+    "ipp_ctree_attach": (C.c_int, [C.POINTER(IppCtree), C.POINTER(IppRollout), C.POINTER(IppRollout), _P]),
+    "ipp_ctree_backup": (C.c_int, [C.POINTER(IppCtree), C.POINTER(IppRollout), _P]),
+    "ipp_ctree_best": (C.c_int, [C.POINTER(IppCtree), _P, _P, _P]),
+    "ipp_ctree_search": (C.c_int, [_P, C.POINTER(IppCtree), C.POINTER(IppRollout), C.POINTER(IppRollout), _P, C.c_uint64, C.c_int32, C.c_int32,
+                                   _P]),
 }
 
 _lib = None

@@ -35,6 +35,7 @@
 #include "k_replay_per.h"
 #include "k_play.h"
 #include "k_rollout.h"
+#include "k_ctree.h"
 #include "k_prepare.h"
 #include "patch_launch.h"
 
@@ -2424,6 +2425,121 @@ int ipp_rollout_run(void* engine, const ipp_rollout* ro, void* scratch, uint64_t
                 return rc;
         }
         if (int rc = ipp_rollout_advance(ro, stream)) return rc;
+    }
+    return 0;
+}
+
+// ---- classic MCTS for a batch, the tree on the device (k_ctree.h)
+static int ctree_check(const ipp_ctree* ct) {
+    if (!ct) return fail(-1, "null ipp_ctree");
+    if (ct->roots <= 0 || ct->cap <= 0 || ct->thr_len <= 0) return fail(-1, "ipp_ctree: roots, cap and thr_len must be positive");
+    if (ct->horizon < 1 || ct->horizon > kTreeDepth) return fail(-1, "ipp_ctree.horizon = %d outside [1, IPP_TREE_DEPTH]", ct->horizon);
+    if ((int64_t)ct->roots * ct->cap > 0x7fffffffll) return fail(-1, "ipp_ctree: roots x cap = %lld slots exceed one table", (long long)ct->roots * ct->cap);
+    if (ct->tree_node_base < 0) return fail(-1, "ipp_ctree.tree_node_base = %d", ct->tree_node_base);
+    if (!ct->thr || !ct->root_slot || !ct->root_wp || !ct->root_budget || !ct->tie_u || !ct->parent || !ct->dev || !ct->plen || !ct->path ||
+        !ct->action || !ct->visits || !ct->value_sum || !ct->edge_reward || !ct->count || !ct->err || !ct->t_len || !ct->t_slot ||
+        !ct->leaf_kind || !ct->leaf_budget || !ct->leaf_depth)
+        return fail(-1, "ipp_ctree: null buffer");
+    return 0;
+}
+
+// a state that travels with the tables: one row per root on the tables' device
+static int ctree_state_check(const ipp_ctree* ct, const ipp_rollout* st, const char* name) {
+    if (int rc = rollout_check(st)) return rc;
+    if (st->n != ct->roots) return fail(-1, "ipp_ctree: %s.n = %d, the tables hold %d roots", name, st->n, ct->roots);
+    if (st->device != ct->device) return fail(-1, "ipp_ctree: %s.device = %d, the tables' is %d", name, st->device, ct->device);
+    return 0;
+}
+
+static int ctree_states_check(const ipp_ctree* ct, const ipp_rollout* expand, const ipp_rollout* rollout) {
+    if (int rc = ctree_check(ct)) return rc;
+    if (int rc = ctree_state_check(ct, expand, "expand")) return rc;
+    if (int rc = ctree_state_check(ct, rollout, "rollout")) return rc;
+    if (expand->max_depth != 1 || expand->gcb != 0) return fail(-1, "ipp_ctree: the expansion state needs max_depth = 1 and gcb = 0");
+    if (rollout->max_depth != ct->horizon) return fail(-1, "ipp_ctree: rollout.max_depth = %d, horizon = %d", rollout->max_depth, ct->horizon);
+    if (expand->kmax != rollout->kmax || expand->half != rollout->half || expand->n_levels != rollout->n_levels)
+        return fail(-1, "ipp_ctree: the two states differ in their candidate square");
+    return 0;
+}
+
+int ipp_ctree_descend(const ipp_ctree* ct, const ipp_rollout* expand, const ipp_rollout* rollout, void* stream) {
+    if (int rc = ctree_states_check(ct, expand, rollout)) return rc;
+    HIP_TRY(hipSetDevice(ct->device));
+    hipLaunchKernelGGL(k_ctree_descend, dim3(ct->roots), dim3(kWave), 0, reinterpret_cast<hipStream_t>(stream), *ct, *expand, *rollout);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ipp_ctree_attach(const ipp_ctree* ct, const ipp_rollout* expand, const ipp_rollout* rollout, void* stream) {
+    if (int rc = ctree_states_check(ct, expand, rollout)) return rc;
+    HIP_TRY(hipSetDevice(ct->device));
+    hipLaunchKernelGGL(k_ctree_attach, dim3((ct->roots + kWave - 1) / kWave), dim3(kWave), 0, reinterpret_cast<hipStream_t>(stream), *ct, *expand,
+                       *rollout);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ipp_ctree_backup(const ipp_ctree* ct, const ipp_rollout* rollout, void* stream) {
+    if (int rc = ctree_check(ct)) return rc;
+    if (int rc = ctree_state_check(ct, rollout, "rollout")) return rc;
+    HIP_TRY(hipSetDevice(ct->device));
+    hipLaunchKernelGGL(k_ctree_backup, dim3((ct->roots + kWave - 1) / kWave), dim3(kWave), 0, reinterpret_cast<hipStream_t>(stream), *ct, *rollout);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ipp_ctree_best(const ipp_ctree* ct, double* action, int32_t* has, void* stream) {
+    if (int rc = ctree_check(ct)) return rc;
+    if (!action || !has) return fail(-1, "null argument");
+    HIP_TRY(hipSetDevice(ct->device));
+    hipLaunchKernelGGL(k_ctree_best, dim3(ct->roots), dim3(kWave), 0, reinterpret_cast<hipStream_t>(stream), *ct, action, has);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ipp_ctree_search(void* engine, const ipp_ctree* ct, const ipp_rollout* expand, const ipp_rollout* rollout, void* scratch,
+                     uint64_t scratch_bytes, int32_t first_sim, int32_t n_sims, void* stream) {
+    Engine* e = as_engine(engine);
+    if (!e) return fail(-1, "null engine");
+    if (int rc = ctree_states_check(ct, expand, rollout)) return rc;
+    if (!e->tree_ok || e->tv.node_cap <= 0) return fail(-1, "%s", kNodesEngineMsg);
+    if (ct->device != e->device) return fail(-1, "ipp_ctree.device = %d, the engine runs on %d", ct->device, e->device);
+    if ((expand->flags | rollout->flags) & ~(uint32_t)(IPP_ADAPTIVE | IPP_USE_FLIGHT_TIME))
+        return fail(-1, "unsupported flag bits 0x%x", expand->flags | rollout->flags);
+    if (first_sim < 0 || n_sims < 0 || (int64_t)first_sim + n_sims > (int64_t)ct->cap - 1)
+        return fail(-1, "simulations [%d, %lld) do not fit cap = %d node slots per root", first_sim, (long long)first_sim + n_sims, ct->cap);
+    const int R = ct->roots;
+    const int64_t tree_lo = ct->tree_node_base, tree_hi = tree_lo + (int64_t)(ct->cap - 1) * R;
+    const int64_t ro_lo = rollout->node_base, ro_hi = ro_lo + (int64_t)R * rollout->max_depth;
+    if (tree_hi > (int64_t)e->tv.node_cap || ro_hi > (int64_t)e->tv.node_cap)
+        return fail(-1, "tree nodes [%lld, %lld) and rollout nodes [%lld, %lld) exceed node_capacity = %d", (long long)tree_lo, (long long)tree_hi,
+                    (long long)ro_lo, (long long)ro_hi, e->tv.node_cap);
+    if (ro_lo < tree_hi && tree_lo < ro_hi)
+        return fail(-1, "tree nodes [%lld, %lld) and rollout nodes [%lld, %lld) overlap", (long long)tree_lo, (long long)tree_hi, (long long)ro_lo,
+                    (long long)ro_hi);
+    const int mb = e->v.max_batch;
+    for (int s = first_sim; s < first_sim + n_sims; ++s) {
+        ipp_ctree c = *ct;
+        ipp_rollout ex = *expand, ro = *rollout;
+        c.tie_u = ct->tie_u + (size_t)s * R * ct->horizon;
+        ex.u = expand->u + (size_t)s * R * 2;
+        ro.u = rollout->u + (size_t)s * R * ct->horizon * 2;
+        ex.node_base = ct->tree_node_base + s * R;
+        if (int rc = ipp_ctree_descend(&c, &ex, &ro, stream)) return rc;
+        if (int rc = ipp_rollout_candidates(&ex, stream)) return rc;
+        if (int rc = ipp_tree_score_nodes(engine, ex.root, ex.path, R, ex.kmax, ex.cand, ex.cur, ex.flags, ex.reward, ex.cost, ex.status, scratch,
+                                          scratch_bytes, stream))
+            return rc;
+        if (int rc = ipp_rollout_pick(&ex, 0, stream)) return rc;
+        for (int o = 0; o < R; o += mb) {  // the recorded step of every expansion (a NaN action: nothing is applied)
+            const int cnt = std::min(mb, R - o);
+            if (int rc = tree_step_impl(engine, ex.root + o, ex.path + (size_t)kTreeDepth * o, ex.new_id + o, cnt, ex.action + 3 * (size_t)o,
+                                        ex.cur + 3 * (size_t)o, ex.flags, ex.step_reward + o, ex.step_status + o, stream, nullptr))
+                return rc;
+        }
+        if (int rc = ipp_ctree_attach(&c, &ex, &ro, stream)) return rc;
+        if (int rc = ipp_rollout_run(engine, &ro, scratch, scratch_bytes, stream)) return rc;
+        if (int rc = ipp_ctree_backup(&c, &ro, stream)) return rc;
     }
     return 0;
 }

@@ -55,21 +55,30 @@ __global__ __launch_bounds__(256) void k_nodes_expand(int n, int k, const int* _
     cost_out[c] = finite_action ? rollout_cost(ax, ay, az, px, py, pz, (flags & IPP_USE_FLIGHT_TIME) != 0, vmax, amax) : rollout_nan();
 }
 
+// candidate j of the (2 half + 1)^2 n_levels square around (cx, cy, cz): its waypoint, and whether it is a candidate at all (in the grid,
+// 3-D distance < radius).  Shared by k_rollout_candidates and the tree kernels' count of available actions (k_ctree.h).
+__device__ __forceinline__ bool rollout_candidate(const ipp_rollout& ro, int j, double cx, double cy, double cz, double& x, double& y,
+                                                  double& z) {
+#pragma clang fp contract(off)
+    const int side = 2 * ro.half + 1;
+    const int off = j / ro.n_levels, lev = j - off * ro.n_levels;
+    const int drow = off / side - ro.half, dcol = off - (off / side) * side - ro.half;
+    const double res = ro.resolution;
+    const double row = floor(cy / res) + (double)drow, col = floor(cx / res) + (double)dcol;
+    x = res * col + 0.5 * res; y = res * row + 0.5 * res; z = ro.levels[lev];
+    const double dx = x - cx, dy = y - cy, dz = z - cz;
+    const double dist = sqrt(dx * dx + dy * dy + dz * dz);  // (np.linalg.norm over the last axis: the three squares in order)
+    return row >= 0.0 && row < (double)ro.grid_h && col >= 0.0 && col < (double)ro.grid_w && dist < ro.radius;
+}
+
 __global__ __launch_bounds__(256) void k_rollout_candidates(ipp_rollout ro) {
 #pragma clang fp contract(off)
     const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= (size_t)ro.n * ro.kmax) return;
     const int i = (int)(c / (size_t)ro.kmax), j = (int)(c - (size_t)i * ro.kmax);
-    const int side = 2 * ro.half + 1;
-    const int off = j / ro.n_levels, lev = j - off * ro.n_levels;
-    const int drow = off / side - ro.half, dcol = off - (off / side) * side - ro.half;
-    const double cx = ro.cur[3 * i + 0], cy = ro.cur[3 * i + 1], cz = ro.cur[3 * i + 2];
-    const double res = ro.resolution;
-    const double row = floor(cy / res) + (double)drow, col = floor(cx / res) + (double)dcol;
-    const double x = res * col + 0.5 * res, y = res * row + 0.5 * res, z = ro.levels[lev];
-    const double dx = x - cx, dy = y - cy, dz = z - cz;
-    const double dist = sqrt(dx * dx + dy * dy + dz * dz);  // (np.linalg.norm over the last axis: the three squares in order)
-    const bool keep = ro.live[i] != 0 && row >= 0.0 && row < (double)ro.grid_h && col >= 0.0 && col < (double)ro.grid_w && dist < ro.radius;
+    double x, y, z;
+    const bool inside = rollout_candidate(ro, j, ro.cur[3 * i + 0], ro.cur[3 * i + 1], ro.cur[3 * i + 2], x, y, z);
+    const bool keep = ro.live[i] != 0 && inside;
     const double nan = rollout_nan();
     ro.cand[3 * c + 0] = keep ? x : nan;
     ro.cand[3 * c + 1] = keep ? y : nan;

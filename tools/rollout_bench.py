@@ -2,13 +2,15 @@
 Times one replan of the classic MCTS planner (planning/mcts_mission.py::ClassicMCTS.replan) for R roots searched in lock step:
   (a) batched=True: device rollouts (csrc/k_rollout.h, planning/device_rollout.py), one ipp_tree_score_nodes call per round
   (b) the default path on a band-tile engine with score_scratch: host rollouts, one ipp_tree_score_actions per scoring request
+  (c) the tree on the device as well (csrc/k_ctree.h, planning/device_ctree.py DeviceClassicMCTS.search): no host read in the search;
+      on the engine of (a), same roots, counts and protocol -- a replan includes drawing and uploading its uniform tables
 and splits a rollout level of (a) into its five calls with device events.
 
-  python tools/rollout_bench.py [--roots 1,16,64] [--sims 100] [--horizon 5] [--reps 3] [--skip-default-above 64] [--out profiles/rollout_bench.txt]
+  python tools/rollout_bench.py [--roots 1,16,64] [--sims 100] [--horizon 5] [--reps 3] [--skip-default-above 64] [--out profiles/ctree_bench.txt]
 
 Roots: 50x50 grids after three measurements, budget 60, altitudes 8 / 14, greedy radius 9 m (98 candidates per node).  Per R the
 median and the min / max of `reps` replans after one warm-up replan, wall clock with the device drained (a replan is host-driven: its
-host time is part of what a user waits for).  The two paths consume their random streams differently, so they do not search the same
+host time is part of what a user waits for).  The paths consume their random streams differently, so they do not search the same
 trees; simulations, horizon and candidate sets are the same.
 """
 import argparse
@@ -69,6 +71,30 @@ def time_replan(torch, mcts, R, prev, reps):
     return np.array(out[1:])
 
 
+def device_planner(cfg, eng, sims, horizon, R):
+    from ipp_rl_amd.planning import DeviceClassicMCTS
+
+    return DeviceClassicMCTS(eng, cfg, UAV, *ALTS, num_simulations=sims, episode_horizon=horizon, max_greedy_radius=RADIUS, adaptive=True, roots=R)
+
+
+def time_device_replan(torch, mcts, R, prev, reps):
+    from ipp_rl_amd.planning.device_ctree import uniform_tables
+
+    out = []
+    wps = torch.as_tensor(np.asarray(prev, dtype=np.float64), device=mcts.engine.device)
+    budgets = torch.full((R,), BUDGET, dtype=torch.float64, device=mcts.engine.device)
+    for rep in range(reps + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        u = uniform_tables(np.random.RandomState(100 + rep), mcts.num_simulations, R, mcts.episode_horizon)
+        mcts.search(list(range(R)), wps, budgets, u)
+        torch.cuda.synchronize()
+        out.append(time.perf_counter() - t0)
+        mcts.check()
+        print(f"    device-tree replan {rep}: {out[-1]:.3f} s", flush=True)
+    return np.array(out[1:])
+
+
 def level_split(torch, eng, R, prev, horizon, reps=3):
     """ms per call of a rollout level for R rollouts from the roots, summed over the levels of a rollout: device events around every call."""
     from ipp_rl_amd.planning.device_rollout import DeviceRollout
@@ -98,14 +124,15 @@ def main():
     ap.add_argument("--sims", type=int, default=100)
     ap.add_argument("--horizon", type=int, default=5)
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--skip-default-above", type=int, default=64)
+    ap.add_argument("--skip-default-above", type=int, default=64, help="0 skips (b) everywhere")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     import torch
 
     lines = [f"ClassicMCTS.replan, R roots of 50x50 in lock step: {args.sims} simulations, horizon {args.horizon}, radius {RADIUS} m, altitudes "
              f"{ALTS[0]:.0f} / {ALTS[1]:.0f}; seconds per replan, median [min, max] of {args.reps} after one warm-up",
-             "R   | (a) batched, device rollouts | (b) default path, band-tile engine | (b) / (a) | (a) rounds, rollout calls, score calls"]
+             "R   | (a) batched, device rollouts | (b) default path, band-tile engine | (b) / (a) | (a) rounds, rollout calls, score calls | "
+             "(c) device tree | (a) / (c) | [min, max] of (c) wholly below that of (a)"]
     split_lines = ["", f"One rollout ({args.horizon} levels) of R rollouts started at the roots, ms per call summed over the levels (device events, "
                    "mean of 3 after a warm-up); share of the level's time",
                    "R   | candidates | score (ipp_tree_score_nodes) | pick | step (ipp_tree_step) | advance"]
@@ -116,6 +143,8 @@ def main():
         ta = time_replan(torch, mcts, R, prev, args.reps)
         st = dict(mcts.stats)
         per = args.reps + 1
+        print(f"R = {R}: device tree", flush=True)
+        tc = time_device_replan(torch, device_planner(cfg, eng, args.sims, args.horizon, R), R, prev, args.reps)
         sp = level_split(torch, eng, R, prev, args.horizon)
         eng.close()
         tot = sum(sp.values())
@@ -130,7 +159,8 @@ def main():
         b_txt = f"{np.median(tb):8.3f} [{tb.min():.3f}, {tb.max():.3f}]" if tb is not None else "not run"
         ratio = f"{np.median(tb) / np.median(ta):.2f}" if tb is not None else "-"
         lines.append(f"{R:3d} | {np.median(ta):8.3f} [{ta.min():.3f}, {ta.max():.3f}] | {b_txt} | {ratio} | {st['rounds'] // per}, "
-                     f"{st['rollout_calls'] // per}, {st['score_calls'] // per}")
+                     f"{st['rollout_calls'] // per}, {st['score_calls'] // per} | {np.median(tc):8.3f} [{tc.min():.3f}, {tc.max():.3f}] | "
+                     f"{np.median(ta) / np.median(tc):.2f} | {'yes' if tc.max() < ta.min() else 'NO'}")
         print(lines[-1], flush=True)
     text = "\n".join(lines + split_lines) + "\n"
     print(text)

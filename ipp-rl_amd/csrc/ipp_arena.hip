@@ -14,21 +14,11 @@
 #include <vector>
 
 #include "../../include/ipp_engine.h"
+#include "ipp_host.h"
 
-namespace ipp { int set_error(int code, const char* msg); }
+using ipp::fail;
 
 namespace {
-
-int failf(int code, const char* what, hipError_t e) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s failed: %s", what, hipGetErrorString(e));
-    return ipp::set_error(code, buf);
-}
-#define ARENA_TRY(expr)                                   \
-    do {                                                  \
-        hipError_t e_ = (expr);                           \
-        if (e_ != hipSuccess) return failf(-2, #expr, e_); \
-    } while (0)
 
 struct Mapping {
     void* reserved = nullptr;      // VMM: start and size of the address reservation (the arena is an aligned range inside it)
@@ -124,21 +114,21 @@ struct ProbeScratch {
 extern "C" {
 
 int ipp_arena_alloc(int device, uint64_t bytes, int32_t kind, uint64_t chunk_bytes, uint64_t align_bytes, void** arena) {
-    if (!arena || bytes == 0) return ipp::set_error(-1, "ipp_arena_alloc: null / empty request");
+    if (!arena || bytes == 0) return fail(-1, "ipp_arena_alloc: null / empty request");
     *arena = nullptr;
-    ARENA_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     Mapping m;
     m.kind = kind; m.device = device; m.bytes = bytes; m.chunk_bytes = 0;
     void* p = nullptr;
     if (kind == IPP_ARENA_HIPMALLOC) {
-        ARENA_TRY(hipMalloc(&p, bytes));
+        HIP_TRY(hipMalloc(&p, bytes));
     } else if (kind == IPP_ARENA_VMM) {
         hipMemAllocationProp prop = {};
         prop.type = hipMemAllocationTypePinned;
         prop.location.type = hipMemLocationTypeDevice;
         prop.location.id = device;
         size_t gran = 0;
-        ARENA_TRY(hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityRecommended));
+        HIP_TRY(hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityRecommended));
         if (gran == 0) gran = 2u << 20;
         uint64_t chunk = chunk_bytes ? chunk_bytes : (uint64_t)1 << 30;
         chunk = (chunk + gran - 1) / gran * gran;
@@ -150,10 +140,10 @@ int ipp_arena_alloc(int device, uint64_t bytes, int32_t kind, uint64_t chunk_byt
         // the reservation's own alignment argument is not honoured beyond the granularity on this runtime (a 1-GiB request came
         // back 160 MiB off): reserve `align` more and map into the aligned range inside
         uint64_t align = align_bytes ? align_bytes : chunk;
-        if (align & (align - 1)) return ipp::set_error(-1, "ipp_arena_alloc: align_bytes must be a power of two");
+        if (align & (align - 1)) return fail(-1, "ipp_arena_alloc: align_bytes must be a power of two");
         if (align < gran) align = gran;
         void* r = nullptr;
-        ARENA_TRY(hipMemAddressReserve(&r, total + align, gran, nullptr, 0));
+        HIP_TRY(hipMemAddressReserve(&r, total + align, gran, nullptr, 0));
         m.reserved = r;
         m.reserved_bytes = total + align;
         p = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(r) + align - 1) / align * align);
@@ -189,7 +179,7 @@ int ipp_arena_alloc(int device, uint64_t bytes, int32_t kind, uint64_t chunk_byt
             }
             if (e != hipSuccess) {
                 undo();
-                return failf(-2, "hipMemCreate / hipMemMap", e);
+                return fail(-2, "%s failed: %s", "hipMemCreate / hipMemMap", hipGetErrorString(e));
             }
             m.chunks.push_back(h);
             m.sizes.push_back(sz);
@@ -201,10 +191,10 @@ int ipp_arena_alloc(int device, uint64_t bytes, int32_t kind, uint64_t chunk_byt
         hipError_t e = hipMemSetAccess(p, total, &acc, 1);
         if (e != hipSuccess) {
             undo();
-            return failf(-2, "hipMemSetAccess", e);
+            return fail(-2, "%s failed: %s", "hipMemSetAccess", hipGetErrorString(e));
         }
     } else {
-        return ipp::set_error(-1, "ipp_arena_alloc: unknown kind");
+        return fail(-1, "ipp_arena_alloc: unknown kind");
     }
     {
         std::lock_guard<std::mutex> g(g_mu);
@@ -220,17 +210,17 @@ int ipp_arena_free(void* arena) {
     {
         std::lock_guard<std::mutex> g(g_mu);
         auto it = g_arenas.find(arena);
-        if (it == g_arenas.end()) return ipp::set_error(-1, "ipp_arena_free: not an arena of ipp_arena_alloc");
+        if (it == g_arenas.end()) return fail(-1, "ipp_arena_free: not an arena of ipp_arena_alloc");
         m = std::move(it->second);
         g_arenas.erase(it);
     }
     if (m.kind == IPP_ARENA_HIPMALLOC) {
-        ARENA_TRY(hipFree(arena));
+        HIP_TRY(hipFree(arena));
         return 0;
     }
     uint64_t off = 0;
     for (size_t i = 0; i < m.chunks.size(); ++i) {
-        ARENA_TRY(hipMemUnmap((char*)arena + off, m.sizes[i]));
+        HIP_TRY(hipMemUnmap((char*)arena + off, m.sizes[i]));
         bool keep = false;
         if (m.sizes[i] == m.chunk_bytes) {  // (whole chunks only: the tail chunk goes back)
             std::lock_guard<std::mutex> g(g_mu);
@@ -240,7 +230,7 @@ int ipp_arena_free(void* arena) {
                 keep = true;
             }
         }
-        if (!keep) ARENA_TRY(hipMemRelease(m.chunks[i]));
+        if (!keep) HIP_TRY(hipMemRelease(m.chunks[i]));
         off += m.sizes[i];
     }
     // The ADDRESS range stays reserved for the life of the process.  Measured on this runtime (ROCm 7.2, gfx950; tools/arena_modes.py,
@@ -268,7 +258,7 @@ int ipp_arena_trim(int device, uint64_t* released) {
         for (auto& x : out) g_pool_bytes -= x.first;
     }
     for (auto& x : out) {
-        ARENA_TRY(hipMemRelease(x.second));
+        HIP_TRY(hipMemRelease(x.second));
         n += x.first;
     }
     if (released) *released = n;
@@ -276,7 +266,7 @@ int ipp_arena_trim(int device, uint64_t* released) {
 }
 
 int ipp_arena_retired_bytes(uint64_t* bytes) {
-    if (!bytes) return ipp::set_error(-1, "null argument");
+    if (!bytes) return fail(-1, "null argument");
     std::lock_guard<std::mutex> g(g_mu);
     *bytes = g_retired_bytes;
     return 0;
@@ -285,55 +275,55 @@ int ipp_arena_retired_bytes(uint64_t* bytes) {
 int ipp_arena_probe(int device, const void* arena, uint64_t bytes, int32_t items, int32_t rows, int32_t launches, void* stream,
                     double* ms) {
     if (!arena || !ms || items < 1 || rows < 1 || launches < 1 || launches > 1000)
-        return ipp::set_error(-1, "ipp_arena_probe: bad argument");
+        return fail(-1, "ipp_arena_probe: bad argument");
     const uint64_t slot_floats = bytes / 4 / (uint64_t)items;
     const uint64_t cols = slot_floats / kPatchFloats;
-    if (cols < 1) return ipp::set_error(-1, "ipp_arena_probe: arena smaller than one patch per item");
-    ARENA_TRY(hipSetDevice(device));
+    if (cols < 1) return fail(-1, "ipp_arena_probe: arena smaller than one patch per item");
+    HIP_TRY(hipSetDevice(device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     ProbeScratch ps;  // (per call: a cached sink would belong to ONE device)
-    ARENA_TRY(hipMalloc(&ps.sink, 64));
-    ARENA_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_arena_probe), hipFuncAttributeMaxDynamicSharedMemorySize, 20480));
-    ARENA_TRY(hipEventCreate(&ps.a));
-    ARENA_TRY(hipEventCreate(&ps.b));
+    HIP_TRY(hipMalloc(&ps.sink, 64));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_arena_probe), hipFuncAttributeMaxDynamicSharedMemorySize, 20480));
+    HIP_TRY(hipEventCreate(&ps.a));
+    HIP_TRY(hipEventCreate(&ps.b));
     float* sink = ps.sink;
     hipEvent_t a = ps.a, b = ps.b;
     const int c = (int)(cols > 0x7fffffff ? 0x7fffffff : cols);
     for (int i = 0; i < 2; ++i)
         hipLaunchKernelGGL(k_arena_probe, dim3(items), dim3(128), 20480, s, (const float*)arena, slot_floats, items, rows, c, sink);
-    ARENA_TRY(hipEventRecord(a, s));
+    HIP_TRY(hipEventRecord(a, s));
     for (int i = 0; i < launches; ++i)
         hipLaunchKernelGGL(k_arena_probe, dim3(items), dim3(128), 20480, s, (const float*)arena, slot_floats, items, rows, c, sink);
-    ARENA_TRY(hipEventRecord(b, s));
-    ARENA_TRY(hipEventSynchronize(b));
+    HIP_TRY(hipEventRecord(b, s));
+    HIP_TRY(hipEventSynchronize(b));
     float t = 0.f;
-    ARENA_TRY(hipEventElapsedTime(&t, a, b));
+    HIP_TRY(hipEventElapsedTime(&t, a, b));
     *ms = (double)t / launches;
-    ARENA_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
 int ipp_arena_latency(int device, const void* arena, uint64_t bytes, int32_t waves, int32_t hops, void* stream, double* ns_per_hop) {
-    if (!arena || !ns_per_hop || waves < 1 || hops < 1) return ipp::set_error(-1, "ipp_arena_latency: bad argument");
+    if (!arena || !ns_per_hop || waves < 1 || hops < 1) return fail(-1, "ipp_arena_latency: bad argument");
     const uint64_t n_patches = bytes / 4 / kPatchFloats;
-    if (n_patches < 1) return ipp::set_error(-1, "ipp_arena_latency: arena smaller than one patch");
-    ARENA_TRY(hipSetDevice(device));
+    if (n_patches < 1) return fail(-1, "ipp_arena_latency: arena smaller than one patch");
+    HIP_TRY(hipSetDevice(device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     ProbeScratch ps;
-    ARENA_TRY(hipMalloc(&ps.sink, 64));
-    ARENA_TRY(hipEventCreate(&ps.a));
-    ARENA_TRY(hipEventCreate(&ps.b));
+    HIP_TRY(hipMalloc(&ps.sink, 64));
+    HIP_TRY(hipEventCreate(&ps.a));
+    HIP_TRY(hipEventCreate(&ps.b));
     float* sink = ps.sink;
     hipEvent_t a = ps.a, b = ps.b;
     hipLaunchKernelGGL(k_arena_latency, dim3(waves), dim3(64), 0, s, (const float*)arena, n_patches, hops, 0u, sink);
-    ARENA_TRY(hipEventRecord(a, s));
+    HIP_TRY(hipEventRecord(a, s));
     hipLaunchKernelGGL(k_arena_latency, dim3(waves), dim3(64), 0, s, (const float*)arena, n_patches, hops, 0u, sink);
-    ARENA_TRY(hipEventRecord(b, s));
-    ARENA_TRY(hipEventSynchronize(b));
+    HIP_TRY(hipEventRecord(b, s));
+    HIP_TRY(hipEventSynchronize(b));
     float t = 0.f;
-    ARENA_TRY(hipEventElapsedTime(&t, a, b));
+    HIP_TRY(hipEventElapsedTime(&t, a, b));
     *ns_per_hop = 1e6 * (double)t / hops;
-    ARENA_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 

@@ -7,28 +7,14 @@
 #include <cstdio>
 
 #include "../../include/ipp_engine.h"
+#include "ipp_host.h"
 #include "k_cmaes.h"
 
-namespace ipp { int set_error(int code, const char* msg); }
+using ipp::fail;
 
 namespace {
 
-int cma_fail(int code, const char* what, hipError_t e) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s failed: %s", what, hipGetErrorString(e));
-    return ipp::set_error(code, buf);
-}
-#define CMA_TRY(expr)                                         \
-    do {                                                      \
-        hipError_t e_ = (expr);                               \
-        if (e_ != hipSuccess) return cma_fail(-2, #expr, e_); \
-    } while (0)
-
-int bad(const char* fn, const char* why) {
-    char buf[200];
-    snprintf(buf, sizeof buf, "%s: %s", fn, why);
-    return ipp::set_error(-1, buf);
-}
+int bad(const char* fn, const char* why) { return fail(-1, "%s: %s", fn, why); }
 
 static_assert(cma::kCmaMaxDim == IPP_CMA_MAX_DIM && cma::kCmaMaxLam == IPP_CMA_MAX_LAMBDA, "header and kernel limits");
 
@@ -54,10 +40,10 @@ int ipp_cma_init(void* state, int32_t n, int32_t nmax, const int32_t* dims, cons
     if (const char* why = check_shape(n, nmax)) return bad("ipp_cma_init", why);
     if (!state || !dims || !m0) return bad("ipp_cma_init", "null argument");
     if (n == 0) return 0;
-    CMA_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     hipLaunchKernelGGL(cma::k_cma_init, dim3((unsigned)n), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), static_cast<double*>(state), nmax,
                        dims, m0);
-    CMA_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -67,10 +53,10 @@ int ipp_cma_ask(const void* state, int32_t n, int32_t nmax, int32_t lam, const f
     if (const char* why = check_lambda(lam)) return bad("ipp_cma_ask", why);
     if (!state || !normals || !scale || !x) return bad("ipp_cma_ask", "null argument");
     if (n == 0) return 0;
-    CMA_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     hipLaunchKernelGGL(cma::k_cma_ask, dim3((unsigned)n), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), static_cast<const double*>(state),
                        nmax, lam, normals, scale, x);
-    CMA_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -84,7 +70,7 @@ int ipp_cma_plan(const int32_t* dims, const double* x, const double* prev, const
     if (use_flight_time && !(max_v > 0 && max_a > 0)) return bad("ipp_cma_plan", "flight time needs max_v > 0 and max_a > 0");
     if (!dims || !x || !prev || !budget || !action || !prev_action || !cost || !path || !live) return bad("ipp_cma_plan", "null argument");
     if (n == 0) return 0;
-    CMA_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     cma::PlanArgs a;
     a.n = n; a.per_env = per_env; a.nmax = nmax; a.horizon = horizon; a.use_flight_time = use_flight_time ? 1 : 0;
     a.x_hi = x_hi; a.y_hi = y_hi; a.z_lo = z_lo; a.z_hi = z_hi; a.vmax = max_v; a.amax = max_a;
@@ -92,7 +78,7 @@ int ipp_cma_plan(const int32_t* dims, const double* x, const double* prev, const
     a.action = action; a.prev_action = prev_action; a.cost = cost; a.path = path; a.live = live;
     const int nc = n * per_env;
     hipLaunchKernelGGL(cma::k_cma_plan, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-    CMA_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -103,10 +89,10 @@ int ipp_cma_objective(const float* reward, const int32_t* status, const double* 
     if (candidates > INT32_MAX / 4) return bad("ipp_cma_objective", "candidates too large");
     if (!reward || !status || !cost || !path || !live || !f) return bad("ipp_cma_objective", "null argument");
     if (candidates == 0) return 0;
-    CMA_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     hipLaunchKernelGGL(cma::k_cma_objective, dim3((unsigned)((candidates + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        candidates, horizon, reward, status, cost, path, live, f);
-    CMA_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -116,10 +102,10 @@ int ipp_cma_tell(void* state, int32_t n, int32_t nmax, int32_t lam, const float*
     if (const char* why = check_lambda(lam)) return bad("ipp_cma_tell", why);
     if (!state || !normals || !x || !f || !scale) return bad("ipp_cma_tell", "null argument");
     if (n == 0) return 0;
-    CMA_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     hipLaunchKernelGGL(cma::k_cma_tell, dim3((unsigned)n), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), static_cast<double*>(state), nmax,
                        lam, normals, x, f, scale);
-    CMA_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 

@@ -206,7 +206,46 @@ struct AutoReset {
     Ledger led;         // IPP_BUDGET launches only (the other instantiations never read it)
 };
 
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t (&k)[2]);  // (k_misc.h)
+// The search driver's use of an item's reward (ipp_mcts_steps): the numerator of the tree edge that asked for the step,
+// t_num[parent][k] = reward (cost + 1) (rewards.py:31 undone: the cost depends on the path that led to the node, the masked trace
+// reduction does not), and a non-zero status into err[2] -- written by k_tree_patch itself instead of by a launch behind it.
+struct TreeEdgeOut {
+    const int* parent; const int* k; const double* cost;  // [n_items] the edge (node, slot) and the cost the reward was divided by
+    double* t_num; int* err; int kmax;                    // t_num == nullptr: off
+    int item_base;  // this launch's items use the per-item scratch slots [item_base, item_base + n) of the engine (overflow records, byte
+                    // counters): two searches stepped on two streams at once must not share them (ipp_mcts_tables.scratch_base)
+};
+
+// Philox4x32-10 counter-based generator + Box-Muller.
+__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t (&k)[2]) {
+    const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
+    const uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
+    const uint32_t hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
+    const uint32_t n0 = hi1 ^ c[1] ^ k[0], n1 = lo1, n2 = hi0 ^ c[3] ^ k[1], n3 = lo0;
+    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+    k[0] += 0x9E3779B9u; k[1] += 0xBB67AE85u;
+}
+
+// The four normals of counter q: Philox4x32-10 of (q, subsequence) under the key `seed`, two Box-Muller pairs (ONE definition for the
+// fill kernels and for the generators that draw their noise in place, so that a number does not depend on who draws it).
+// log / sin / cos through the hardware's transcendental units (v_log_f32, v_sin_f32 / v_cos_f32 take the angle in revolutions: no range
+// reduction): 1e-6 of a standard normal against the library calls, which were a third of the 100x100 field generator's instructions.
+__device__ __forceinline__ void philox_normal4(uint64_t q, uint64_t subseq, uint64_t seed, float (&nrm)[4]) {
+    uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32), (uint32_t)subseq, (uint32_t)(subseq >> 32)};
+    uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+#pragma unroll
+    for (int r = 0; r < 10; ++r) philox_round(c, k);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const float u0 = ((float)c[2 * h] + 0.5f) * 2.3283064365386963e-10f;
+        const float u1 = ((float)c[2 * h + 1] + 0.5f) * 2.3283064365386963e-10f;
+        const float rad = sqrtf(-2.0f * __logf(fmaxf(u0, 1e-30f)));
+        float sn, cs;
+        __sincosf(6.283185307179586f * u1, &sn, &cs);
+        nrm[2 * h] = rad * cs;
+        nrm[2 * h + 1] = rad * sn;
+    }
+}
 
 // Start budget of episode `episode` of env `env` (sample_budget, episode_generators.py:113 with shuffle_budget:
 // int(U(10, initial_budget))): floor(10 + u (b0 - 10)), u the Philox4x32-10 uniform of counter (env + row_offset),

@@ -1,0 +1,29 @@
+// Host-side internals shared by the library's five translation units: the one error slot behind ipp_last_error, and the narrow view
+// of an engine that the search calls (ipp_search.hip) need.  No kernels.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace ipp {
+int fail(int code, const char* fmt, ...);  // formats the calling thread's ipp_last_error message, returns `code` (ipp_engine.hip)
+
+#define HIP_TRY(expr)                                                                                \
+    do {                                                                                             \
+        hipError_t e_ = (expr);                                                                      \
+        if (e_ != hipSuccess) return ipp::fail(-2, "%s failed: %s", #expr, hipGetErrorString(e_));   \
+    } while (0)
+
+struct TreeEngine {  // read at every call (ipp_set_uav changes vmax / amax)
+    int device, max_batch, node_cap;
+    bool tree_ok, patch;  // ipp_tree_step available; tree nodes as patches (k_tree_patch.h)
+    double vmax, amax;
+};
+int tree_engine(void* engine, TreeEngine* out);  // (null engine: "null engine")
+
+// ipp_tree_step + the search driver's extras: the item count on the device (n_dev), the edge numerators written by the patch kernel
+// itself (edge_out: ipp_common.h); either may be NULL
+struct TreeEdgeOut;
+int tree_step(void* engine, const int32_t* root_ids, const int32_t* path_ids, const int32_t* new_ids, int32_t n, const double* action,
+              const double* prev_action, uint32_t flags, float* reward, int32_t* status, void* stream, const int32_t* n_dev,
+              const TreeEdgeOut* edge_out);
+}  // namespace ipp

@@ -10,23 +10,13 @@
 #include <vector>
 
 #include "../../include/ipp_engine.h"
+#include "ipp_host.h"
 #include "k_pvnet.h"
 #include "k_train.h"
 
-namespace ipp { int set_error(int code, const char* msg); }
+using ipp::fail;
 
 namespace {
-
-int pv_fail(int code, const char* what, hipError_t e) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s failed: %s", what, hipGetErrorString(e));
-    return ipp::set_error(code, buf);
-}
-#define PV_TRY(expr)                                        \
-    do {                                                    \
-        hipError_t e_ = (expr);                             \
-        if (e_ != hipSuccess) return pv_fail(-2, #expr, e_); \
-    } while (0)
 
 constexpr int kBuffers = 3, kSlots = 2, kMaxKmax = 8192;
 
@@ -48,11 +38,7 @@ struct PvNet {
     }
 };
 
-int bad_plan(int i, const char* why) {
-    char buf[200];
-    snprintf(buf, sizeof buf, "ipp_pvnet_create: op %d: %s", i, why);
-    return ipp::set_error(-1, buf);
-}
+int bad_plan(int i, const char* why) { return fail(-1, "ipp_pvnet_create: op %d: %s", i, why); }
 
 // every condition a launch relies on, checked once: an invalid plan fails here and never at launch
 int validate(PvNet& net) {
@@ -119,19 +105,19 @@ int validate(PvNet& net) {
             (o.kind == IPP_PV_OP_VALUE ? has_value : has_policy) = true;
         }
     }
-    if (net.in_c == 0) return ipp::set_error(-1, "ipp_pvnet_create: the plan does not start with a conv on the planes");
-    if (!has_value || !has_policy) return ipp::set_error(-1, "ipp_pvnet_create: the plan lacks a value or a policy head");
+    if (net.in_c == 0) return fail(-1, "ipp_pvnet_create: the plan does not start with a conv on the planes");
+    if (!has_value || !has_policy) return fail(-1, "ipp_pvnet_create: the plan lacks a value or a policy head");
     return 0;
 }
 
 int upload(PvNet& net, const float* weights, hipStream_t s) {
-    PV_TRY(hipMemcpyAsync(net.w, weights, net.n_floats * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(net.w, weights, net.n_floats * sizeof(float), hipMemcpyHostToDevice, s));
     if (net.precision == IPP_PV_BF16) {
         const unsigned blocks = (unsigned)((net.n_floats + 255) / 256);
         hipLaunchKernelGGL(pv::k_pv_to_bf16, dim3(blocks), dim3(256), 0, s, net.w, net.wbf, (unsigned long long)net.n_floats);
-        PV_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
-    PV_TRY(hipStreamSynchronize(s));  // the host blob may go away when the call returns
+    HIP_TRY(hipStreamSynchronize(s));  // the host blob may go away when the call returns
     return 0;
 }
 
@@ -141,18 +127,18 @@ extern "C" {
 
 int ipp_pvnet_create(const ipp_pvnet_op* ops, int32_t n_ops, const float* weights, uint64_t n_floats, int32_t precision, int32_t max_batch,
                      int32_t device, void** out) {
-    if (!ops || !weights || !out || n_ops < 1 || n_floats < 1) return ipp::set_error(-1, "ipp_pvnet_create: null / empty argument");
+    if (!ops || !weights || !out || n_ops < 1 || n_floats < 1) return fail(-1, "ipp_pvnet_create: null / empty argument");
     *out = nullptr;
-    if (precision != IPP_PV_FP32 && precision != IPP_PV_BF16) return ipp::set_error(-1, "ipp_pvnet_create: unknown precision");
-    if (max_batch < 1) return ipp::set_error(-1, "ipp_pvnet_create: max_batch < 1");
-    if (n_floats > ((uint64_t)1 << 31)) return ipp::set_error(-1, "ipp_pvnet_create: weight blob too large");
+    if (precision != IPP_PV_FP32 && precision != IPP_PV_BF16) return fail(-1, "ipp_pvnet_create: unknown precision");
+    if (max_batch < 1) return fail(-1, "ipp_pvnet_create: max_batch < 1");
+    if (n_floats > ((uint64_t)1 << 31)) return fail(-1, "ipp_pvnet_create: weight blob too large");
     PvNet* net = new PvNet;
     net->device = device; net->precision = precision; net->max_batch = max_batch; net->n_floats = n_floats;
     net->ops.assign(ops, ops + n_ops);
     int rc = validate(*net);
-    if (rc == 0 && net->buf_floats * (uint64_t)max_batch >= ((uint64_t)1 << 40)) rc = ipp::set_error(-1, "ipp_pvnet_create: activation buffers too large");
+    if (rc == 0 && net->buf_floats * (uint64_t)max_batch >= ((uint64_t)1 << 40)) rc = fail(-1, "ipp_pvnet_create: activation buffers too large");
     if (rc != 0) { delete net; return rc; }
-    auto guard = [&](hipError_t e, const char* what) { if (e == hipSuccess) return 0; delete net; return pv_fail(-2, what, e); };
+    auto guard = [&](hipError_t e, const char* what) { if (e == hipSuccess) return 0; delete net; return fail(-2, "%s failed: %s", what, hipGetErrorString(e)); };
     if ((rc = guard(hipSetDevice(device), "hipSetDevice"))) return rc;
     if ((rc = guard(hipMalloc(&net->w, n_floats * sizeof(float)), "hipMalloc(weights)"))) return rc;
     if (precision == IPP_PV_BF16 && (rc = guard(hipMalloc(&net->wbf, n_floats * sizeof(unsigned short)), "hipMalloc(bf16 weights)"))) return rc;
@@ -167,21 +153,21 @@ int ipp_pvnet_create(const ipp_pvnet_op* ops, int32_t n_ops, const float* weight
 
 int ipp_pvnet_set_weights(void* handle, const float* weights, uint64_t n_floats, void* stream) {
     PvNet* net = static_cast<PvNet*>(handle);
-    if (!net || !weights) return ipp::set_error(-1, "ipp_pvnet_set_weights: null argument");
-    if (n_floats != net->n_floats) return ipp::set_error(-1, "ipp_pvnet_set_weights: the blob's size differs from the plan's");
-    PV_TRY(hipSetDevice(net->device));
+    if (!net || !weights) return fail(-1, "ipp_pvnet_set_weights: null argument");
+    if (n_floats != net->n_floats) return fail(-1, "ipp_pvnet_set_weights: the blob's size differs from the plan's");
+    HIP_TRY(hipSetDevice(net->device));
     return upload(*net, weights, reinterpret_cast<hipStream_t>(stream));
 }
 
 int ipp_pvnet_forward(void* handle, const float* planes, int32_t n, const int32_t* valid_idx, int32_t kmax, double* prior, double* value,
                       int32_t tap_op, float* tap_out, void* stream) {
     PvNet* net = static_cast<PvNet*>(handle);
-    if (!net || !planes || !valid_idx || !prior || !value) return ipp::set_error(-1, "ipp_pvnet_forward: null argument");
-    if (n < 0) return ipp::set_error(-1, "ipp_pvnet_forward: n < 0");
-    if (kmax < 1 || kmax > kMaxKmax) return ipp::set_error(-1, "ipp_pvnet_forward: kmax out of range");
+    if (!net || !planes || !valid_idx || !prior || !value) return fail(-1, "ipp_pvnet_forward: null argument");
+    if (n < 0) return fail(-1, "ipp_pvnet_forward: n < 0");
+    if (kmax < 1 || kmax > kMaxKmax) return fail(-1, "ipp_pvnet_forward: kmax out of range");
     if (tap_op != -1 && (tap_op < 0 || tap_op >= (int)net->ops.size() || net->ops[tap_op].kind != IPP_PV_OP_CONV || !tap_out))
-        return ipp::set_error(-1, "ipp_pvnet_forward: tap_op must be a conv op of the plan, with tap_out");
-    PV_TRY(hipSetDevice(net->device));
+        return fail(-1, "ipp_pvnet_forward: tap_op must be a conv op of the plan, with tap_out");
+    HIP_TRY(hipSetDevice(net->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const uint64_t plane_floats = (uint64_t)net->in_c * net->in_h * net->in_w;
     const void* wts = net->precision == IPP_PV_BF16 ? static_cast<const void*>(net->wbf) : static_cast<const void*>(net->w);
@@ -228,7 +214,7 @@ int ipp_pvnet_forward(void* handle, const float* planes, int32_t n, const int32_
                                    valid_idx + (uint64_t)c0 * kmax, kmax, prior + (uint64_t)c0 * kmax, value + c0);
             }
         }
-        PV_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     return 0;
 }
@@ -237,14 +223,14 @@ int ipp_pvnet_loss(const float* logits, const float* target_policy, const uint8_
                    const double* target_value, const double* target_reward, const double* weights, int32_t n, int32_t num_actions,
                    double policy_coeff, double value_coeff, double reward_coeff, double entropy_coeff, double* stats, float* grad_logits,
                    float* grad_value, float* grad_reward, int32_t device, void* stream) {
-    if (n < 0) return ipp::set_error(-1, "ipp_pvnet_loss: n < 0");
-    if (num_actions < 1) return ipp::set_error(-1, "ipp_pvnet_loss: num_actions < 1");
+    if (n < 0) return fail(-1, "ipp_pvnet_loss: n < 0");
+    if (num_actions < 1) return fail(-1, "ipp_pvnet_loss: num_actions < 1");
     if (!logits || !target_policy || !valid_msk || !value || !target_value || !weights || !stats || !grad_logits || !grad_value)
-        return ipp::set_error(-1, "ipp_pvnet_loss: null argument");
+        return fail(-1, "ipp_pvnet_loss: null argument");
     if ((reward == nullptr) != (target_reward == nullptr) || (reward == nullptr) != (grad_reward == nullptr))
-        return ipp::set_error(-1, "ipp_pvnet_loss: reward, target_reward and grad_reward are given together or not at all");
+        return fail(-1, "ipp_pvnet_loss: reward, target_reward and grad_reward are given together or not at all");
     if (n == 0) return 0;
-    PV_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     pvt::LossArgs a;
     a.n = n; a.A = num_actions;
     a.logits = logits; a.target_policy = target_policy; a.valid_msk = valid_msk; a.value = value; a.reward = reward;
@@ -252,28 +238,25 @@ int ipp_pvnet_loss(const float* logits, const float* target_policy, const uint8_
     a.pc = policy_coeff; a.vc = value_coeff; a.rc = reward_coeff; a.ec = entropy_coeff;
     a.stats = stats; a.grad_logits = grad_logits; a.grad_value = grad_value; a.grad_reward = grad_reward;
     hipLaunchKernelGGL(pvt::k_pv_loss, dim3((unsigned)n), dim3(pvt::kThreads), 0, reinterpret_cast<hipStream_t>(stream), a);
-    PV_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
 int ipp_pvnet_sgd_step(float* params, const float* grads, float* momentum_buf, int64_t n, double lr, double momentum, double weight_decay,
                        double max_norm, double* norm_out, double* scratch, uint64_t scratch_doubles, int32_t device, void* stream) {
     static_assert(pvt::kSgdMaxBlocks == IPP_PVNET_SGD_SCRATCH, "scratch bound");
-    if (n < 0) return ipp::set_error(-1, "ipp_pvnet_sgd_step: n < 0");
-    if (!params || !grads || !momentum_buf || !norm_out || !scratch) return ipp::set_error(-1, "ipp_pvnet_sgd_step: null argument");
+    if (n < 0) return fail(-1, "ipp_pvnet_sgd_step: n < 0");
+    if (!params || !grads || !momentum_buf || !norm_out || !scratch) return fail(-1, "ipp_pvnet_sgd_step: null argument");
     const int blocks = pvt::sgd_blocks(n);
-    if (scratch_doubles < (uint64_t)blocks) {
-        char buf[160];
-        snprintf(buf, sizeof buf, "ipp_pvnet_sgd_step: scratch of %llu doubles, %d needed", (unsigned long long)scratch_doubles, blocks);
-        return ipp::set_error(-1, buf);
-    }
+    if (scratch_doubles < (uint64_t)blocks)
+        return fail(-1, "ipp_pvnet_sgd_step: scratch of %llu doubles, %d needed", (unsigned long long)scratch_doubles, blocks);
     if (n == 0) return 0;
-    PV_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(pvt::k_sgd_partial, dim3(blocks), dim3(pvt::kThreads), 0, s, grads, (long long)n, scratch);
     hipLaunchKernelGGL(pvt::k_sgd_update, dim3(blocks), dim3(pvt::kThreads), 0, s, params, grads, momentum_buf, (long long)n, lr, momentum,
                        weight_decay, max_norm, (const double*)scratch, norm_out);
-    PV_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 

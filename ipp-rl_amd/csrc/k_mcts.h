@@ -713,4 +713,55 @@ __global__ __launch_bounds__(256) void k_mcts_policy(ipp_mcts_tables m, const do
     if (lane == 0) ok[j] = tot > 0 ? 1 : 0;
 }
 
+// ---------------------------------------------------------------------------------------------------- search leaves
+// History entries of the pending leaves of a wave of simulations (DeviceMCTS(feature_planes=True)), slot g = root j * wave + s:
+// the leaf, then the nodes of the descent that reached it (pend_sim -> p_node / p_k / p_cost, deepest first, the root node last),
+// then the root's own earlier states (root_history[j][1 ..], the env's ring entries, when given), zero padding after that.
+// A node's state is its root env slot plus its device path n_devpath (the root node: the slot itself); its waypoint the action
+// of the edge that led to it (prev0 at the root); its budget budget0 minus the descent's costs above it, over initial_budget.
+// Slots without a pending leaf are all padding.  mask_env[g] = root_env[j] (the map mean of the reference's get_adaptive_info).
+__global__ __launch_bounds__(256) void k_mcts_plane_entries(ipp_mcts_tables m, const int32_t* __restrict__ root_env,
+                                                            const double* __restrict__ prev0, const double* __restrict__ budget0,
+                                                            const ipp_plane_entry* __restrict__ root_hist, int H, double b0, int sim0,
+                                                            ipp_plane_entry* __restrict__ out, int32_t* __restrict__ mask_env) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= m.roots * m.wave) return;
+    const int j = g / m.wave, s = g - j * m.wave;
+    ipp_plane_entry* o = out + (size_t)g * H;
+    ipp_plane_entry pad{};
+    for (int q = 0; q < kTreeDepth; ++q) pad.path[q] = -1;
+    int h = 0;
+    if (mask_env) mask_env[g] = root_env[j];
+    if (s < m.pend_count[j]) {
+        const int w = m.pend_sim[g] - sim0;
+        const int plen = (w >= 0 && w < m.wave) ? min(m.p_len[w * m.roots + j], m.max_depth) : 0;
+        const size_t pb = ((size_t)w * m.roots + j) * m.max_depth;
+        auto node_entry = [&](int node, const double* pos, double budget) {
+            ipp_plane_entry e = pad;
+            e.root_env = root_env[j];
+            e.rank = -1;
+            for (int q = 0; q < kTreeDepth; ++q) e.path[q] = m.n_devpath[(size_t)kTreeDepth * node + q];
+            e.valid = 1;
+            e.position[0] = pos[0]; e.position[1] = pos[1]; e.position[2] = pos[2];
+            e.budget = budget / b0;
+            return e;
+        };
+        o[h++] = node_entry(m.pend_node[g], m.pend_prev + 3 * (size_t)g, m.pend_budget[g]);
+        for (int a = plen - 1; a >= 0 && h < H; --a) {
+            double budget = budget0[j];  // (the select kernel's order: budget -= cost per edge)
+            for (int e = 0; e < a; ++e) budget -= m.p_cost[pb + e];
+            const double* pos = prev0 + 3 * (size_t)j;
+            if (a > 0) {
+                const int parent = m.p_node[pb + a - 1];
+                const int a_idx = m.t_idx[(size_t)parent * m.kmax + m.p_k[pb + a - 1]];
+                pos = m.actions + 3 * (size_t)a_idx;
+            }
+            o[h++] = node_entry(m.p_node[pb + a], pos, budget);
+        }
+        if (root_hist && h < H && (plen > 0 || m.pend_node[g] == j * m.nodes_per_root))  // (the root node has been pushed)
+            for (int q = 1; q < H && h < H; ++q) o[h++] = root_hist[(size_t)j * H + q];
+    }
+    for (; h < H; ++h) o[h] = pad;
+}
+
 }  // namespace ipp

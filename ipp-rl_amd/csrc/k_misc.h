@@ -339,16 +339,6 @@ __global__ __launch_bounds__(256) void k_metrics(View v, const int* __restrict__
     }
 }
 
-// Philox4x32-10 counter-based generator + Box-Muller.
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t (&k)[2]) {
-    const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-    const uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
-    const uint32_t hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
-    const uint32_t n0 = hi1 ^ c[1] ^ k[0], n1 = lo1, n2 = hi0 ^ c[3] ^ k[1], n3 = lo0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-    k[0] += 0x9E3779B9u; k[1] += 0xBB67AE85u;
-}
-__device__ __forceinline__ void philox_normal4(uint64_t q, uint64_t subseq, uint64_t seed, float (&nrm)[4]);
 __global__ void k_fill_normal(float* __restrict__ out, uint64_t count, uint64_t seed, uint64_t subseq) {
     const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q * 4 >= count) return;
@@ -356,27 +346,6 @@ __global__ void k_fill_normal(float* __restrict__ out, uint64_t count, uint64_t 
     philox_normal4(q, subseq, seed, nrm);
     for (int e = 0; e < 4; ++e)
         if (q * 4 + e < count) out[q * 4 + e] = nrm[e];
-}
-
-// The four normals of counter q: Philox4x32-10 of (q, subsequence) under the key `seed`, two Box-Muller pairs (ONE definition for the
-// fill kernels and for the generators that draw their noise in place, so that a number does not depend on who draws it).
-// log / sin / cos through the hardware's transcendental units (v_log_f32, v_sin_f32 / v_cos_f32 take the angle in revolutions: no range
-// reduction): 1e-6 of a standard normal against the library calls, which were a third of the 100x100 field generator's instructions.
-__device__ __forceinline__ void philox_normal4(uint64_t q, uint64_t subseq, uint64_t seed, float (&nrm)[4]) {
-    uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32), (uint32_t)subseq, (uint32_t)(subseq >> 32)};
-    uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
-#pragma unroll
-    for (int r = 0; r < 10; ++r) philox_round(c, k);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const float u0 = ((float)c[2 * h] + 0.5f) * 2.3283064365386963e-10f;
-        const float u1 = ((float)c[2 * h + 1] + 0.5f) * 2.3283064365386963e-10f;
-        const float rad = sqrtf(-2.0f * __logf(fmaxf(u0, 1e-30f)));
-        float sn, cs;
-        __sincosf(6.283185307179586f * u1, &sn, &cs);
-        nrm[2 * h] = rad * cs;
-        nrm[2 * h + 1] = rad * sn;
-    }
 }
 
 // Row-keyed variant: out[p][j][c] (planes x rows x row_len) = normal(seed, subsequence subseq0 + p, counter =

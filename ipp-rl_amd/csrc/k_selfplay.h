@@ -12,7 +12,6 @@
 // Every draw is a Philox4x32-10 uniform keyed on the GLOBAL env id (include/ipp_engine.h, IPP_SP_*_STREAM), so shards agree.
 #pragma once
 #include "ipp_common.h"
-#include "k_misc.h"
 
 namespace ipp {
 

@@ -69,16 +69,6 @@ struct TreeIo {
     }
 };
 
-// The search driver's use of an item's reward (ipp_mcts_steps): the numerator of the tree edge that asked for the step,
-// t_num[parent][k] = reward (cost + 1) (rewards.py:31 undone: the cost depends on the path that led to the node, the masked trace
-// reduction does not), and a non-zero status into err[2] -- written by the kernel itself instead of by a launch behind it.
-struct TreeEdgeOut {
-    const int* parent; const int* k; const double* cost;  // [n_items] the edge (node, slot) and the cost the reward was divided by
-    double* t_num; int* err; int kmax;                    // t_num == nullptr: off
-    int item_base;  // this launch's items use the per-item scratch slots [item_base, item_base + n) of the engine (overflow records, byte
-                    // counters): two searches stepped on two streams at once must not share them (ipp_mcts_tables.scratch_base)
-};
-
 template <int NW, int RJN = 0>  // (RJN: k_step_patch.h)
 __global__ __launch_bounds__(64 * NW, kPatchMinW) void k_tree_patch(
     View v, TreeView tv, const int* __restrict__ root_ids, const int* __restrict__ path_ids, const int* __restrict__ new_ids,

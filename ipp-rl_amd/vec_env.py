@@ -42,7 +42,7 @@ def _as_u64(x) -> np.ndarray:
 
 def philox_words(counter, subsequence, seed: int):
     """Philox4x32-10 (Salmon et al., SC'11) of the 128-bit counter (counter, subsequence) under the 64-bit key `seed`: the four 32-bit
-    output words as uint64 arrays, the host copy of the ten rounds of philox_normal4 (csrc/k_misc.h).  counter / subsequence: ints or
+    output words as uint64 arrays, the host copy of the ten rounds of philox_normal4 (csrc/ipp_common.h).  counter / subsequence: ints or
     int arrays (broadcast; negative values count as their 64-bit two's complement)."""
     m32 = np.uint64(0xFFFFFFFF)
     q, sub = np.broadcast_arrays(_as_u64(counter), _as_u64(subsequence))
@@ -65,7 +65,7 @@ def philox_uniform(counter, subsequence, seed: int) -> np.ndarray:
 
 
 def philox_normal4_ref(counter, subsequence, seed: int) -> np.ndarray:
-    """The four standard normals of every counter, float64 [..., 4]: the DEFINITION of the device's philox_normal4 (csrc/k_misc.h), not
+    """The four standard normals of every counter, float64 [..., 4]: the DEFINITION of the device's philox_normal4 (csrc/ipp_common.h), not
     its instructions.  Uniforms as the device forms them, in float32: u = (float(word) + 0.5f) * 2^-32; from there in float64, Box-Muller
     of the pairs (word 0, word 1) and (word 2, word 3): rad = sqrt(-2 log(max(u0, 1e-30))), angle 2 pi u1, elements
     (rad0 cos0, rad0 sin0, rad1 cos1, rad1 sin1)."""

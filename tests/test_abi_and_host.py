@@ -116,6 +116,27 @@ def test_arena_calls_validate_their_arguments_without_gpu():
     assert engine.ARENA_VMM_MIN_BYTES == 256 << 20
 
 
+@pytest.mark.parametrize("unit,call,args,message", [
+    ("ipp_engine", "ipp_engine_arena_bytes", (None, None), b"null argument"),
+    ("ipp_search", "ipp_mcts_backup", (None, 1, None), b"null tables"),
+    ("ipp_search", "ipp_rollout_pick", (None, 0, None), b"null rollout"),
+    ("ipp_search", "ipp_ctree_best", (None, None, None, None), b"null ipp_ctree"),
+    ("ipp_arena", "ipp_arena_alloc", (0, 0, 1, 0, 0, None), b"ipp_arena_alloc: null / empty request"),
+    ("ipp_pvnet", "ipp_pvnet_set_weights", (None, None, 0, None), b"ipp_pvnet_set_weights: null argument"),
+    ("ipp_cmaes", "ipp_cma_state_bytes", (4, None), b"ipp_cma_state_bytes: null argument"),
+])
+def test_every_translation_unit_reports_through_the_one_error_slot(unit, call, args, message):
+    """The library is linked from five translation units (csrc/ipp_<unit>.hip) and has ONE thread-local error string, beside
+    ipp_last_error in the engine unit: a validation failure in any unit returns -1 and leaves its message there for the calling
+    thread.  Every call here fails on its arguments, before the first device call."""
+    from ipp_rl_amd import _ffi
+
+    lib = _ffi.load()
+    assert lib.ipp_arena_free(ctypes.c_void_p(0x1000)) == -1 and lib.ipp_last_error() != message  # (another message in the slot first)
+    assert getattr(lib, call)(*args) == -1
+    assert lib.ipp_last_error() == message
+
+
 def test_tree_patches_stay_within_reach_of_their_32_bit_record_offsets():
     """k_tree_patch addresses a column patch by a 32-bit offset in 8-byte units from View::cov: root slots and node blocks have to lie
     within 2^35 bytes of it.  The decision is taken on the finished arena layout (the score scratch -- one dense P, 17 GB at

@@ -1,5 +1,5 @@
 """
-The device's normals (philox_normal4, csrc/k_misc.h: Philox4x32-10, then Box-Muller through the hardware log / sin / cos) element by
+The device's normals (philox_normal4, csrc/ipp_common.h: Philox4x32-10, then Box-Muller through the hardware log / sin / cos) element by
 element against the fp64 restatement of their definition on the host (vec_env.philox_normal4_ref; its Philox words are pinned to the
 Random123 known answers in tests/test_normals_host.py): the flat fill, the row-keyed fill (counter = (row id + offset) * ceil(row_len / 4)
 + c // 4, element c % 4, plane p in subsequence subseq0 + p), every high word of counter, subsequence and seed, and the words at which

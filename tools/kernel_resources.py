@@ -20,5 +20,5 @@ for line in txt.splitlines():
     else:
         cur["Spill" if k == "VGPRs Spill" else k.split(" ")[0]] = val
 for r in rows:
-    name = subprocess.run(["c++filt", r["name"]], capture_output=True, text=True).stdout.strip().split("(")[0]
+    name = subprocess.run(["c++filt", r["name"]], capture_output=True, text=True).stdout.strip().replace("(anonymous namespace)::", "").split("(")[0]
     print(f"{name:45s} VGPR={r.get('VGPRs'):>4s} AGPR={r.get('AGPRs'):>3s} SGPR={r.get('TotalSGPRs'):>4s} scratch={r.get('ScratchSize'):>5s} occ={r.get('Occupancy')} spill={r.get('Spill')} LDS={r.get('LDS')}")

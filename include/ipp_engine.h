@@ -1232,6 +1232,92 @@ int ipp_ctree_best(const ipp_ctree* ct, double* action, int32_t* has, void* stre
 int ipp_ctree_search(void* engine, const ipp_ctree* ct, const ipp_rollout* expand, const ipp_rollout* rollout, void* scratch,
                      uint64_t scratch_bytes, int32_t first_sim, int32_t n_sims, void* stream);
 
+/*
+ * Baselines and comparison curves (csrc/k_baselines.h, csrc/k_curves.h; bare device buffers, no engine handle but for the metrics of
+ * ipp_curve_record).
+ *
+ * ipp_baseline_act: ONE decision per env of a batch for one of the reference's four baseline missions, on the ledger arrays installed by
+ * ipp_set_budget (`budget`, `episode`).  Replaces create_waypoints + the budget tests of execute of
+ *   IPP_BASELINE_LAWNMOWER          planning/baselines/lawn_mower_mission.py:66-114 and :124-131: the next row of `table` while
+ *                                   cursor < table_len and budget >= step_size and budget > cost(next, prev)
+ *   IPP_BASELINE_SPIRAL             planning/baselines/conical_spiral_mission.py:67-108: the next row of `table` while cursor < table_len
+ *                                   and (cursor == 0 or budget - cost(next, prev) >= 0); the first waypoint is flown whatever it costs
+ *   IPP_BASELINE_RANDOM_DISCRETE    planning/baselines/random_discrete_mission.py:73-107: over the A = n_levels grid_w grid_h actions of
+ *                                   enumerate_actions (planning/common/actions.py:73-91; action h N + grid_w xc + yc is the waypoint
+ *                                   (resolution xc + resolution / 2, resolution yc + resolution / 2, levels[h]), square grids), the mask
+ *                                   0 < d <= budget and d < 11.5 (d: distance), adaptive: 0 < t <= budget (t: flight time); with `count`
+ *                                   valid actions the one of rank min(floor(u count), count - 1) in index order; none when count == 0
+ *   IPP_BASELINE_RANDOM_CONTINUOUS  planning/baselines/random_continuous_mission.py:68-101 and :118: IPP_BASELINE_TRIALS trial waypoints
+ *                                   low + (high - low) u_t, the first with budget - cost >= 0, else the last one; an action when
+ *                                   budget >= 0 and budget > cost(chosen)
+ * cost = action_costs (planning/common/actions.py:8-12): the flight time with use_flight_time, else the distance.  The tables are built on
+ * the host at budget = +inf (planning/vec_baselines.py).  An env whose episode[e] differs from seen_episode[e] (a reset on the device)
+ * starts again at cursor 0 and latches start_budget[e] = budget[e]; decision[e] counts the calls and is never reset.  An env without
+ * an action: action[e] = prev[e], has[e] = 0, budget[e] = 0 -- the env's own rule then ends its episode on the next budget step.
+ * uniforms: [n] (discrete) / [n][IPP_BASELINE_TRIALS][3] (continuous) in [0, 1), or NULL: Philox4x32-10, first word, of counter
+ * 512 (env + row_offset) + 4 trial + component in subsequence IPP_BASELINE_STREAM + decision[e] under the key `seed`.
+ */
+#define IPP_BASELINE_STREAM (10ull << 40) /* Philox subsequence base of the random baselines' uniforms */
+#define IPP_BASELINE_LAWNMOWER         0
+#define IPP_BASELINE_SPIRAL            1
+#define IPP_BASELINE_RANDOM_DISCRETE   2
+#define IPP_BASELINE_RANDOM_CONTINUOUS 3
+#define IPP_BASELINE_TRIALS 101 /* the first draw + trials = 100 redraws (random_continuous_mission.py:80-93) */
+typedef struct ipp_baseline {
+    int32_t n;                /* envs */
+    int32_t kind;             /* IPP_BASELINE_* */
+    int32_t table_len;        /* rows of table (table kinds) */
+    int32_t grid_w, grid_h;   /* cells along x / y (discrete) */
+    int32_t n_levels;         /* altitude levels (discrete) */
+    int32_t adaptive;         /* discrete: the flight-time mask */
+    int32_t use_flight_time;  /* table kinds, continuous: the cost mode (the engine's UAV setting) */
+    int32_t device;
+    int32_t reserved;
+    double resolution, step_size, max_v, max_a;
+    double low[3], high[3];   /* continuous: the sampling box */
+    uint64_t seed;
+    int64_t row_offset;       /* global id of env 0 */
+    const double* table;      /* [table_len][3] */
+    const double* levels;     /* [n_levels] */
+    const double* uniforms;   /* or NULL: Philox */
+    const double* prev;       /* [n][3] current waypoints */
+    double* budget;           /* [n] the ledger's budgets */
+    const int64_t* episode;   /* [n] the ledger's episode indices */
+    int32_t* cursor; int64_t* seen_episode; int64_t* decision; double* start_budget;   /* [n] the policy's own arrays */
+    double* action;           /* [n][3] out */
+    uint8_t* has;             /* [n] out */
+} ipp_baseline;
+int ipp_baseline_act(const ipp_baseline* bl, void* stream);
+
+/*
+ * Metric curves per env and their comparison (experiments/experiments.py:194-236: every run's metrics against its cumulative flight
+ * time, np.interp onto one axis, mean and spread per planner; the points are those of Mission.eval, planning/missions.py:176-203).
+ * log [dev] double[n][t_cap][IPP_CURVE_POINT] = (cumulative flight time, the 8 values of ipp_metrics), count [dev] int32[n],
+ * overflow [dev] uint8[n]; the caller zeroes count and overflow once.
+ *
+ * ipp_curve_record appends one point for every env with executed[e] != 0: time = previous time + compute_flight_time(action[e],
+ * prev_before[e]) (planning/common/actions.py:32-41 -- flight time whatever the cost mode, experiments.py:219), values = metrics[e]
+ * widened.  first != 0: the step-0 point (time 0, eval(run_time=0, flight_time=0)) for EVERY env; action / prev_before / executed may be
+ * NULL.  engine != NULL: metrics [dev] float[n][8] is filled by ipp_metrics of the env slots 0 .. n - 1 first; NULL: the caller filled it.
+ * A full log sets overflow[e] and drops the point.
+ */
+#define IPP_CURVE_VALUES 8
+#define IPP_CURVE_POINT  9
+int ipp_curve_record(void* engine, float* metrics, const double* action, const double* prev_before, const uint8_t* executed, int32_t n,
+                     int32_t first, double max_v, double max_a, double* log, int32_t* count, uint8_t* overflow, int32_t t_cap, int32_t device,
+                     void* stream);
+/* max_x_all [dev] double[1] = the largest last recorded time of the envs (experiments.py:227: max([np.max(x) for x in xs])); 0 when nothing is recorded */
+int ipp_curve_extent(const double* log, const int32_t* count, int32_t n, int32_t t_cap, double* max_x_all, int32_t device, void* stream);
+/* out [dev] double[n][grid][8] = np.interp(np.linspace(0, max_x, grid), xs_e, ys_e) per env and value (experiments.py:228-229): with j the
+ * largest index with xs[j] <= x: ys[last] for j = last, else (ys[j+1] - ys[j]) / (xs[j+1] - xs[j]) (x - xs[j]) + ys[j]; ys[0] left of xs[0];
+ * an env with an empty log gets NaN. */
+int ipp_curve_resample(const double* log, const int32_t* count, int32_t n, int32_t t_cap, double max_x, int32_t grid, double* out,
+                       int32_t device, void* stream);
+/* mean, sd [dev] double[grid][8] over the n envs of per_env [n][grid][8] (the band of the line plot, experiments.py:238-244; sd with
+ * ddof = 1, 0 for n = 1), summed in a fixed order: two runs give the same bits.  (The largest flight time is ipp_curve_extent's alone:
+ * the axis, and with it `grid`, is sized from it before anything is resampled.) */
+int ipp_curve_reduce(const double* per_env, int32_t n, int32_t grid, double* mean, double* sd, int32_t device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

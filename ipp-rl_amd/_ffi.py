@@ -165,6 +165,23 @@ class IppCtree(C.Structure):
     ]
 
 
+class IppBaseline(C.Structure):
+    """ipp_baseline (include/ipp_engine.h): kind, geometry, cost mode and the [dev] arrays of one baseline decision per env."""
+    _fields_ = [
+        ("n", C.c_int32), ("kind", C.c_int32), ("table_len", C.c_int32), ("grid_w", C.c_int32), ("grid_h", C.c_int32),
+        ("n_levels", C.c_int32), ("adaptive", C.c_int32), ("use_flight_time", C.c_int32), ("device", C.c_int32), ("reserved", C.c_int32),
+        ("resolution", C.c_double), ("step_size", C.c_double), ("max_v", C.c_double), ("max_a", C.c_double),
+        ("low", C.c_double * 3), ("high", C.c_double * 3), ("seed", C.c_uint64), ("row_offset", C.c_int64),
+        ("table", _P), ("levels", _P), ("uniforms", _P), ("prev", _P), ("budget", _P), ("episode", _P),
+        ("cursor", _P), ("seen_episode", _P), ("decision", _P), ("start_budget", _P), ("action", _P), ("has", _P),
+    ]
+
+
+IPP_BASELINE_STREAM = 10 << 40  # Philox subsequence base of the random baselines' uniforms (planning/vec_baselines.py)
+IPP_BASELINE_LAWNMOWER, IPP_BASELINE_SPIRAL, IPP_BASELINE_RANDOM_DISCRETE, IPP_BASELINE_RANDOM_CONTINUOUS = 0, 1, 2, 3
+IPP_BASELINE_TRIALS = 101
+IPP_CURVE_VALUES, IPP_CURVE_POINT = 8, 9
+
 IPP_CTREE_TERMINAL, IPP_CTREE_ROLLOUT, IPP_CTREE_EXPAND = 0, 1, 2
 IPP_CTREE_ERR_RANGE, IPP_CTREE_ERR_SELECT, IPP_CTREE_ERR_PICK, IPP_CTREE_ERR_STEP, IPP_CTREE_ERR_FULL, IPP_CTREE_ERR_ROLLOUT = 1, 2, 3, 4, 5, 6
 
@@ -287,6 +304,12 @@ PROTOTYPES = {
     "ipp_ctree_best": (C.c_int, [C.POINTER(IppCtree), _P, _P, _P]),
     "ipp_ctree_search": (C.c_int, [_P, C.POINTER(IppCtree), C.POINTER(IppRollout), C.POINTER(IppRollout), _P, C.c_uint64, C.c_int32, C.c_int32,
                                    _P]),
+    # (the baseline missions and the comparison curves, csrc/k_baselines.h and csrc/k_curves.h: added without an ABI bump as well)
+    "ipp_baseline_act": (C.c_int, [C.POINTER(IppBaseline), _P]),
+    "ipp_curve_record": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, _P, _P, C.c_int32, C.c_int32, _P]),
+    "ipp_curve_extent": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
+    "ipp_curve_resample": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_double, C.c_int32, _P, C.c_int32, _P]),
+    "ipp_curve_reduce": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P]),
 }
 
 _lib = None

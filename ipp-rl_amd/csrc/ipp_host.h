@@ -1,4 +1,4 @@
-// Host-side internals shared by the library's five translation units: the one error slot behind ipp_last_error, and the narrow view
+// Host-side internals shared by the library's six translation units: the one error slot behind ipp_last_error, and the narrow view
 // of an engine that the search calls (ipp_search.hip) need.  No kernels.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -888,6 +888,47 @@ int ipp_replay_priority_update(const ipp_selfplay* sp, double* priority, const i
                                void* stream);
 
 /*
+ * Self-play ITERATIONS (csrc/k_selfplay.h, csrc/k_learn.h): the episodes of one pass of the learn loop,
+ * planning/mcts_zero/mcts_zero_mission.py:305-362 (`num_episodes` episodes per worker and iteration, their samples under
+ * train_data/iter_{i}), and the off-policy window over iterations, ReplayBuffer(self_play_iteration, window_size),
+ * replay_buffers.py:34-46.  Here every env plays `episode_cap` episodes per iteration and every committed ring row carries the
+ * iteration it came from.  The state is the caller's, all arrays [dev]; each env owns its own counters (no atomics).  The calls were
+ * added without an ABI bump: nothing existing changes layout.
+ */
+typedef struct ipp_selfplay_iter {
+    int32_t  iteration, episode_cap;
+    int32_t* iter_episodes;   /* [dev] [num_envs]  episodes of env e ended in this iteration */
+    int32_t* r_iter;          /* [dev] [slots * num_envs]  iteration tag of a committed row */
+    int64_t* examples;        /* [dev] [num_envs]  rows kept in this iteration */
+    double*  value_sum;       /* [dev] [num_envs]  sum of total_episode_value of the kept episodes */
+} ipp_selfplay_iter;
+
+/*
+ * ipp_selfplay_commit with the iteration rule.  When env e's episode of T rows ends: keep = iter_episodes[e] < episode_cap.  A kept
+ * episode gets its value targets as in ipp_selfplay_commit; each of its rows gets r_iter[row] = iteration and then the committed flag
+ * (in that order, by the same thread); examples[e] += T, value_sum[e] += the episode's total value.  An episode past the cap is
+ * dropped: its rows get flag 0 and no targets.  In both cases iter_episodes[e] += 1, also for T = 0 (an env that can never move does
+ * not stall the iteration).  Everything else -- the reward into the row, episode_value, ep_len, the next first waypoint, tie_u, the
+ * forced end -- is ipp_selfplay_commit's.  Refused (-1, nothing written): what ipp_selfplay_commit refuses, a NULL `it` or array,
+ * episode_cap < 1.
+ */
+int ipp_selfplay_commit_iter(const ipp_selfplay* sp, int64_t step, const ipp_selfplay_iter* it, void* stream);
+/*
+ * The iteration's progress in one record, out [dev] 32 bytes = {int64 episodes_kept (sum of min(iter_episodes, episode_cap)), int64
+ * envs_at_cap (envs with iter_episodes >= episode_cap), int64 examples, double value_sum}.  One workgroup; the fp64 sum runs over the
+ * envs in ascending order in the fixed order of ipp_replay_mass's scan (chunks of 256 envs: a shuffle scan inside each wave of 64,
+ * the four waves' sums in wave order, the chunks' sums in chunk order): no floating-point atomics, the same bits in every run.
+ */
+int ipp_selfplay_iter_totals(const ipp_selfplay* sp, const ipp_selfplay_iter* it, void* out, void* stream);
+/*
+ * ipp_replay_priority_reset restricted to the window lo <= r_iter[row] <= hi: count <- L = the rows that are committed AND tagged
+ * inside the window, priority <- 1 / L on them and 0 on every other row (a row outside the window has no mass for ipp_replay_mass /
+ * ipp_replay_draw_per).  r_iter [dev] int32 [S B].  Refused (-1, nothing written): a NULL array, lo > hi.
+ */
+int ipp_replay_priority_reset_window(const ipp_selfplay* sp, const int32_t* r_iter, int32_t lo, int32_t hi, double* priority,
+                                     uint64_t* count, void* stream);
+
+/*
  * Playing with a trained network (csrc/k_play.h): the decision of the deployment planner, MCTSZeroMission.replan,
  * planning/mcts_zero/mcts_zero_mission.py:504-523 (`workers` root-parallel searches per decision, their policies summed, normalised,
  * arg-max), and the game bookkeeping of the arena gate, planning/mcts_zero/arenas.py:25-56, for every env of a budget-mode batch at once.

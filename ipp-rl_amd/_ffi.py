@@ -123,6 +123,19 @@ class IppSelfPlay(C.Structure):
     ]
 
 
+class IppSelfPlayIter(C.Structure):
+    """ipp_selfplay_iter (include/ipp_engine.h): the cap, the per-env counters and the row tags of a self-play iteration, [dev] pointers."""
+    _fields_ = [
+        ("iteration", C.c_int32), ("episode_cap", C.c_int32),
+        ("iter_episodes", _P), ("r_iter", _P), ("examples", _P), ("value_sum", _P),
+    ]
+
+
+class IppIterTotals(C.Structure):
+    """The 32-byte record of ipp_selfplay_iter_totals."""
+    _fields_ = [("episodes_kept", C.c_int64), ("envs_at_cap", C.c_int64), ("examples", C.c_int64), ("value_sum", C.c_double)]
+
+
 class IppPlay(C.Structure):
     """ipp_play (include/ipp_engine.h): the deployment planner's / arena's per-env decision and game bookkeeping, [dev] pointers."""
     _fields_ = [
@@ -268,6 +281,10 @@ PROTOTYPES = {
                                       _P, _P, _P]),
     "ipp_replay_gather_rows": (C.c_int, [C.POINTER(IppSelfPlay), C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ipp_replay_priority_update": (C.c_int, [C.POINTER(IppSelfPlay), _P, _P, _P, C.c_int32, _P]),
+    # (self-play iterations and the off-policy window, csrc/k_selfplay.h and csrc/k_learn.h: added without an ABI bump as well)
+    "ipp_selfplay_commit_iter": (C.c_int, [C.POINTER(IppSelfPlay), C.c_int64, C.POINTER(IppSelfPlayIter), _P]),
+    "ipp_selfplay_iter_totals": (C.c_int, [C.POINTER(IppSelfPlay), C.POINTER(IppSelfPlayIter), _P, _P]),
+    "ipp_replay_priority_reset_window": (C.c_int, [C.POINTER(IppSelfPlay), _P, C.c_int32, C.c_int32, _P, _P, _P]),
     # (the deployment planner's and the arena's calls, csrc/k_play.h: added without an ABI bump, nothing existing changes layout)
     "ipp_play_pick": (C.c_int, [C.POINTER(IppPlay), _P, _P, _P, _P]),
     "ipp_play_tally": (C.c_int, [C.POINTER(IppPlay), _P]),

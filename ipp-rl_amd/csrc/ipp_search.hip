@@ -8,6 +8,7 @@
 #include "k_mcts.h"
 #include "k_selfplay.h"
 #include "k_replay_per.h"
+#include "k_learn.h"
 #include "k_play.h"
 #include "k_rollout.h"
 #include "k_ctree.h"
@@ -280,6 +281,53 @@ int ipp_replay_priority_update(const ipp_selfplay* sp, double* priority, const i
     HIP_TRY(hipSetDevice(sp->device));
     hipLaunchKernelGGL(k_per_update, dim3((unsigned)((n + kPerThreads - 1) / kPerThreads)), dim3(kPerThreads), 0,
                        reinterpret_cast<hipStream_t>(stream), (long long)sp->num_envs * sp->slots, (int)n, index, value, priority);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- self-play iterations and the off-policy window (k_sp_commit_iter in k_selfplay.h, k_learn.h)
+static int selfplay_iter_check(const ipp_selfplay_iter* it) {
+    if (!it) return fail(-1, "null argument");
+    if (it->episode_cap < 1) return fail(-1, "ipp_selfplay_iter: episode_cap = %d < 1", it->episode_cap);
+    if (!it->iter_episodes || !it->r_iter || !it->examples || !it->value_sum) return fail(-1, "ipp_selfplay_iter: null device pointer");
+    return 0;
+}
+
+int ipp_selfplay_commit_iter(const ipp_selfplay* sp, int64_t step, const ipp_selfplay_iter* it, void* stream) {
+    if (int rc = selfplay_check(sp)) return rc;
+    if (int rc = selfplay_iter_check(it)) return rc;
+    if (step < 0) return fail(-1, "step = %lld < 0", (long long)step);
+    HIP_TRY(hipSetDevice(sp->device));
+    hipLaunchKernelGGL(k_sp_commit_iter, dim3(sp->num_envs), dim3(kWave), 0, reinterpret_cast<hipStream_t>(stream), *sp, (long long)step, *it);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ipp_selfplay_iter_totals(const ipp_selfplay* sp, const ipp_selfplay_iter* it, void* out, void* stream) {
+    if (int rc = replay_ring_check(sp)) return rc;
+    if (int rc = selfplay_iter_check(it)) return rc;
+    if (!out) return fail(-1, "null argument");
+    HIP_TRY(hipSetDevice(sp->device));
+    hipLaunchKernelGGL(k_sp_iter_totals, dim3(1), dim3(kPerThreads), 0, reinterpret_cast<hipStream_t>(stream), (int)sp->num_envs, *it,
+                       reinterpret_cast<IterTotals*>(out));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ipp_replay_priority_reset_window(const ipp_selfplay* sp, const int32_t* r_iter, int32_t lo, int32_t hi, double* priority,
+                                     uint64_t* count, void* stream) {
+    if (int rc = replay_ring_check(sp)) return rc;
+    if (!r_iter || !priority || !count) return fail(-1, "null argument");
+    if (lo > hi) return fail(-1, "window [%d, %d]: lo > hi", lo, hi);
+    const long long cap = (long long)sp->num_envs * sp->slots;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(sp->device));
+    HIP_TRY(hipMemsetAsync(count, 0, sizeof(uint64_t), s));
+    const unsigned blocks = (unsigned)((cap + kPerThreads - 1) / kPerThreads);
+    hipLaunchKernelGGL(k_per_count_win, dim3(blocks), dim3(kPerThreads), 0, s, sp->r_flags, r_iter, (int)lo, (int)hi, cap,
+                       reinterpret_cast<unsigned long long*>(count));
+    hipLaunchKernelGGL(k_per_reset_win, dim3(blocks), dim3(kPerThreads), 0, s, sp->r_flags, r_iter, (int)lo, (int)hi, cap,
+                       reinterpret_cast<const unsigned long long*>(count), priority);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -6,6 +6,8 @@
 //   k_sp_commit   one wave per env: the step's reward into its row; for every env whose episode ended the windowed value targets of
 //                 all its rows in fp64 (:158-164), the committed flags, the episode's value, the next episode's first waypoint
 //                 (sample_init_action, :51, :60-62) and the next step's tie-break uniform
+//   k_sp_commit_iter  the same body with the iteration rule of the learn loop (mcts_zero_mission.py:320-340; k_learn.h holds the rest):
+//                 an env keeps episode_cap episodes per iteration, their rows tagged with it; later ones are dropped
 //   k_sp_gather   store-bound: minibatch rows drawn uniformly from the committed ones, planes shifted by ReplicationPad2d(4) +
 //                 RandomCrop (one offset per augmented copy), policies and masks densified to [A]; k_sp_gather_rows: the same rows
 //                 for a given index array (the prioritised sampler, k_replay_per.h)
@@ -146,7 +148,11 @@ __global__ __launch_bounds__(64) void k_sp_record(ipp_selfplay sp, long long ste
     }
 }
 
-__global__ __launch_bounds__(64) void k_sp_commit(ipp_selfplay sp, long long step) {
+// The commit of env e by its wave.  ITER = false: k_sp_commit.  ITER = true: k_sp_commit_iter, the same with the iteration rule of
+// ipp_selfplay_commit_iter (include/ipp_engine.h): an episode past the env's cap is dropped, a kept one tags its rows and counts;
+// `it` is read in that instantiation only.
+template <bool ITER>
+__device__ __forceinline__ void sp_commit_body(const ipp_selfplay& sp, long long step, const ipp_selfplay_iter* it) {
 #pragma clang fp contract(off)
     const int e = blockIdx.x, lane = threadIdx.x;
     if (e >= sp.num_envs) return;
@@ -161,13 +167,22 @@ __global__ __launch_bounds__(64) void k_sp_commit(ipp_selfplay sp, long long ste
         const long long t_last = forced ? step - 1 : step;
         auto row_of = [&](int j) { return (size_t)((t_last - (T - 1 - j)) % S) * B + e; };
         auto r_of = [&](int j) { return (j == T - 1 && !forced) ? r_now : sp.r_reward[row_of(j)]; };
+        bool keep = true;
+        if constexpr (ITER) keep = it->iter_episodes[e] < it->episode_cap;  // (every lane reads it before lane 0 counts the episode)
         // value_i = sum_{j = i}^{min(i + horizon, T) - 1} gamma^j r_j: the ABSOLUTE step j as exponent (episode_generators.py:163)
         for (int i = lane; i < T; i += 64) {
+            if constexpr (ITER) {
+                if (!keep) {  // past the cap: the episode is played out but leaves no sample
+                    sp.r_flags[row_of(i)] = 0;
+                    continue;
+                }
+            }
             const int hi = min(i + sp.horizon, T);
             double v = 0.0;
             for (int j = i; j < hi; ++j) v += sp_discount(sp.gamma, j) * r_of(j);
             const size_t r = row_of(i);
             sp.r_value[r] = sqrt(1.0 + v) - 1.0;  // scale_value_target (planning/common/rewards.py)
+            if constexpr (ITER) it->r_iter[r] = it->iteration;
             sp.r_flags[r] = kSpCommitted;          // (behind its target: a row becomes sampleable with its value written)
         }
         if (lane == 0) {
@@ -175,6 +190,13 @@ __global__ __launch_bounds__(64) void k_sp_commit(ipp_selfplay sp, long long ste
             for (int j = 0; j < T; ++j) tot += sp_discount(sp.gamma, j) * r_of(j);
             sp.episode_value[e] = tot;
             sp.ep_len[e] = 0;
+            if constexpr (ITER) {
+                if (keep) {
+                    it->examples[e] += T;
+                    it->value_sum[e] += tot;
+                }
+                it->iter_episodes[e] += 1;  // (also for T = 0: an env that can never move does not stall the iteration)
+            }
             if (sp.random_init) {  // the episode the step's reset started: its first waypoint, uniform over the action set
                 const double u = sp_uniform((uint64_t)gid, IPP_SP_INIT_STREAM + (uint64_t)ep, sp.seed);
                 int a = (int)(u * (double)sp.num_actions);
@@ -189,6 +211,13 @@ __global__ __launch_bounds__(64) void k_sp_commit(ipp_selfplay sp, long long ste
         sp.forced[e] = 0;
         sp.tie_u[e] = sp_uniform(sp_step_counter(gid, sp.depth[e]), IPP_SP_TIE_STREAM + (uint64_t)ep, sp.seed);
     }
+}
+
+__global__ __launch_bounds__(64) void k_sp_commit(ipp_selfplay sp, long long step) { sp_commit_body<false>(sp, step, nullptr); }
+
+// the commit of a self-play iteration (mcts_zero_mission.py:320-340: num_episodes episodes per worker, here episode_cap per env)
+__global__ __launch_bounds__(64) void k_sp_commit_iter(ipp_selfplay sp, long long step, ipp_selfplay_iter it) {
+    sp_commit_body<true>(sp, step, &it);
 }
 
 // Minibatch row of draw i: the floor(u total)-th committed row (cum = inclusive prefix count of the committed flags), -1 when

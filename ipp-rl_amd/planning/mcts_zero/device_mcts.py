@@ -172,6 +172,26 @@ class DeviceMCTS(VectorMCTS):
                               K=pin((R,), torch.int32), nodes=pin((), torch.int64))
         return tab, b
 
+    def set_exploration(self, puct_init: float, dirichlet_alpha: float):
+        """The scheduled exploration parameters of a learn iteration (mcts_zero_mission.py:231-243: hyper_params['puct_init'] and
+        ['dirichlet_alpha'] change between iterations, and the reference builds its searches from them anew).  Re-derives what the
+        constructor and _alloc bake from them -- the `puct_init + log(...)` table, ipp_mcts_tables.puct_init, the Dirichlet alpha
+        of the expansion -- here and in every sub-search of groups > 1; env, node tables and streams stay.  On the current stream:
+        a search issued afterwards equals that of a DeviceMCTS constructed with these values."""
+        import torch
+
+        self.puct_init, self.alpha = float(puct_init), float(dirichlet_alpha)
+        hp = dict(self._ctor["hyper_params"], puct_init=self.puct_init, dirichlet_alpha=self.alpha)
+        self.hp = hp
+        self._ctor = dict(self._ctor, hyper_params=hp)  # (sub-searches built later start from the new values)
+        if self._tab is not None:
+            self._tab.puct_init = self.puct_init
+            ns = np.arange(int(self._tab.ns_table_n), dtype=np.float64)
+            self._ns_tables[0].copy_(torch.as_tensor(self.puct_init + np.log((ns + self.puct_base + 1) / self.puct_base),
+                                                     device=self._ns_tables[0].device))  # (in place: the table's address stays)
+        for sub in self._subs or []:
+            sub.set_exploration(puct_init, dirichlet_alpha)
+
     # ------------------------------------------------------------------ search
     def get_policy(self, roots: Sequence[int], previous_actions, budgets, depth: int = 0, temperature: float = 1.0,
                    deploy_time: bool = False, rngs=None, as_arrays: bool = False, root_history=None):

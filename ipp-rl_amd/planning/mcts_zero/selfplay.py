@@ -26,6 +26,13 @@ ExperienceReplayBuffer) and ReplayBuffer.prioritized (PrioritizedExperienceRepla
 prefix sums, the draws, the importance-sampling weights and the priority updates all in device memory; a trainer's use_per selects it,
 the episode loop has no use for the switch and check_args refuses it).
 
+Iterations of the learn loop (mcts_zero_mission.py:305-362: `num_episodes` episodes per worker and iteration, their samples under
+train_data/iter_{i}; ReplayBuffer(self_play_iteration, window_size), replay_buffers.py:34-46): SelfPlay.begin_iteration / step_iteration /
+run_iteration commit with ipp_selfplay_commit_iter -- every env keeps `episodes_per_env` episodes per iteration, their rows tagged with
+the iteration in ReplayBuffer.iter, later episodes are played out and dropped -- and read the iteration's totals record
+(ipp_selfplay_iter_totals) from pinned memory, the step's one new read.  ReplayBuffer.window(lo, hi) serves a Trainer the rows of
+iterations lo .. hi (planning/mcts_zero/learn.py).
+
 Divergences from the reference (INTEGRATION.md "Batched self-play"): a temperature-0 sample stores the real valid-action mask where the
 reference stores the visit counts (mcts.py:138); no tree reuse between steps, no per-episode shuffled priors; the draws are counter-based,
 not NumPy's global stream.
@@ -167,6 +174,82 @@ def shift_planes(states: np.ndarray, offset) -> np.ndarray:
     return pad[..., i:i + h, j:j + w]
 
 
+def commit_iter_host(state: Dict, step: int, it: Dict) -> Dict:
+    """ipp_selfplay_commit_iter on NumPy arrays.  state: the ring and env fields in front of the commit (B, S, A, gamma, horizon,
+    random_init, seed, row_offset; reward, forced, done, ep_len, episode, depth, actions, prev, r_reward, r_value, r_flags); it:
+    iteration, episode_cap, iter_episodes, r_iter, examples, value_sum.  Returns what the call leaves: r_reward, r_value, r_flags, ep_len,
+    prev, episode_value (NaN: nothing ended), forced, tie_u and iter_episodes, r_iter, examples, value_sum.  An episode that ends is
+    kept while the env has fewer than episode_cap ended episodes in this iteration: targets, tag, then the committed flag, examples += T,
+    value_sum += total_episode_value; past the cap its rows get flag 0 and nothing else; either way it counts (T = 0 too)."""
+    B, S, A = int(state["B"]), int(state["S"]), int(state["A"])
+    out = {k: np.array(state[k]) for k in ("r_reward", "r_value", "r_flags", "ep_len", "prev")}
+    out.update(iter_episodes=np.array(it["iter_episodes"], dtype=np.int32), r_iter=np.array(it["r_iter"], dtype=np.int32),
+               examples=np.array(it["examples"], dtype=np.int64), value_sum=np.array(it["value_sum"], dtype=np.float64))
+    out["episode_value"] = np.full(B, np.nan)
+    out["forced"] = np.zeros(B, np.uint8)
+    gid = np.arange(B, dtype=np.int64) + int(state["row_offset"])
+    cap, iteration = int(it["episode_cap"]), int(it["iteration"])
+    for e in range(B):
+        forced = bool(state["forced"][e])
+        if not forced:
+            out["r_reward"][(step % S) * B + e] = float(state["reward"][e])
+        if not (forced or state["done"][e]):
+            continue
+        T = int(state["ep_len"][e])
+        t_last = step - 1 if forced else step
+        rows = np.array([((t_last - (T - 1 - j)) % S) * B + e for j in range(T)], dtype=np.int64)
+        vals, tot = value_targets(out["r_reward"][rows], state["gamma"], state["horizon"])
+        if out["iter_episodes"][e] < cap:
+            out["r_value"][rows], out["r_iter"][rows], out["r_flags"][rows] = vals, iteration, COMMITTED
+            out["examples"][e] += T
+            out["value_sum"][e] += tot
+        else:
+            out["r_flags"][rows] = 0
+        out["iter_episodes"][e] += 1
+        out["episode_value"][e], out["ep_len"][e] = tot, 0
+        if state["random_init"]:
+            out["prev"][e] = state["actions"][int(init_action_index(state["seed"], gid[e], int(state["episode"][e]), A))]
+    out["tie_u"] = step_uniform(TIE_STREAM, state["seed"], gid, state["episode"], state["depth"])
+    return out
+
+
+def scan_order_sum(values) -> float:
+    """The fp64 sum of ipp_selfplay_iter_totals, in its order (that of ipp_replay_mass's scan of the tile sums): chunks of 256 values in
+    ascending order, zeros behind the last; in a chunk each wave of 64 runs a shuffle scan (for o = 1, 2, .. 32: v[l] += v[l - o]) whose
+    last lane holds the wave's sum, the four wave sums are added in wave order to 0, and the chunks' totals in chunk order to 0."""
+    v = np.asarray(values, dtype=np.float64).reshape(-1)
+    carry = np.float64(0.0)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for c0 in range(0, len(v), 256):
+            chunk = np.zeros(256)
+            chunk[:len(v[c0:c0 + 256])] = v[c0:c0 + 256]
+            tot = np.float64(0.0)
+            for w in range(4):
+                x = chunk[64 * w:64 * w + 64].copy()
+                o = 1
+                while o < 64:
+                    x[o:] = x[o:] + x[:-o]  # (the right-hand side is evaluated before the assignment: every lane adds the old value)
+                    o *= 2
+                tot = tot + x[63]
+            carry = carry + tot
+    return float(carry)
+
+
+def iter_totals_host(iter_episodes, examples, value_sum, episode_cap: int) -> Dict:
+    """ipp_selfplay_iter_totals: episodes_kept = sum min(iter_episodes, cap), envs_at_cap = #(iter_episodes >= cap), examples = the sum
+    of the kept rows, value_sum = scan_order_sum of the envs' value sums."""
+    n = np.asarray(iter_episodes, dtype=np.int64)
+    return dict(episodes_kept=int(np.minimum(n, int(episode_cap)).sum()), envs_at_cap=int((n >= int(episode_cap)).sum()),
+                examples=int(np.asarray(examples, dtype=np.int64).sum()), value_sum=scan_order_sum(value_sum))
+
+
+def window_rows_host(flags, r_iter, lo: int, hi: int) -> np.ndarray:
+    """Ascending ring rows of the off-policy window [lo, hi] (ReplayBuffer(self_play_iteration, window_size), replay_buffers.py:34-46):
+    committed and tagged with an iteration inside it.  ipp_replay_priority_reset_window gives these L rows 1 / L and every other row 0."""
+    f, t = np.asarray(flags), np.asarray(r_iter, dtype=np.int64)
+    return np.nonzero((f == COMMITTED) & (t >= int(lo)) & (t <= int(hi)))[0].astype(np.int64)
+
+
 def check_args(hyper_params: Dict, meta_data: Dict, num_envs: int, capacity: Optional[int]):
     """What SelfPlay cannot run, refused before anything touches the device.  Returns (slots S, max_episode_steps)."""
     if meta_data.get("initial_budget") is None:
@@ -221,6 +304,7 @@ class ReplayBuffer:
         self.value = e((cap,), torch.float64)
         self.reward = e((cap,), torch.float64)
         self.flags = e((cap,), torch.uint8)
+        self.iter = torch.full((cap,), -1, dtype=torch.int32, device=device)  # self-play iteration a committed row came from (-1: none)
         self._owner = owner
         self.draws = 0
         self.last_offsets = None
@@ -234,6 +318,10 @@ class ReplayBuffer:
         """Device int64 indices of the committed rows, ascending."""
         return self.torch.nonzero(self.flags == COMMITTED).reshape(-1)
 
+    def window(self, lo: int, hi: int) -> "ReplayWindow":
+        """The rows of self-play iterations lo .. hi (ReplayBuffer(self_play_iteration, window_size), replay_buffers.py:34-46): a view
+        with the members a Trainer uses (len, sample, prioritized).  A ring that never saw an iteration has an empty window."""
+        return ReplayWindow(self, lo, hi)
 
     def prioritized(self, batch_size: int = 32, alpha: float = 0.75, beta0: float = 0.5, num_epochs: int = 3) -> "PrioritizedReplay":
         """PrioritizedExperienceReplayBuffer (replay_buffers.py:104-141) over the rows committed now; reads their count from the device
@@ -245,15 +333,20 @@ class ReplayBuffer:
         indices i64 (ring rows), weights (ones, f64)) -- ExperienceReplayBuffer.sample with augment_random_crop: b = max(1, batch_size //
         (k + 1)) rows drawn uniformly with replacement from the committed rows, originals first, then k shifted copies.  states is None
         without planes.  check_empty reads the committed count from the device and raises on an empty buffer (else the rows are -1 / NaN)."""
+        return self._sample(self.flags == COMMITTED, batch_size, num_augmented_samples, check_empty,
+                            "the replay buffer holds no committed sample yet (no episode has ended)")
+
+    def _sample(self, sampleable, batch_size: int, num_augmented_samples: int, check_empty: bool, empty: str):
+        """sample() over the rows of the device mask `sampleable`."""
         torch = self.torch
         k = int(num_augmented_samples)
         if k < 0:
             raise ValueError("num_augmented_samples must be >= 0")
         n = max(1, int(batch_size) // (k + 1))
         copies = k + 1
-        cum = torch.cumsum((self.flags == COMMITTED).to(torch.int32), 0, dtype=torch.int32)
+        cum = torch.cumsum(sampleable.to(torch.int32), 0, dtype=torch.int32)
         if check_empty and int(cum[-1].item()) == 0:
-            raise ValueError("the replay buffer holds no committed sample yet (no episode has ended)")
+            raise ValueError(empty)
         dev, rows = self.flags.device, n * copies
         states = torch.empty((rows, self.channels, self.side, self.side), dtype=torch.float32, device=dev) if self.channels else None
         pol = torch.empty((rows, self.num_actions), dtype=torch.float32, device=dev)
@@ -279,6 +372,37 @@ class ReplayBuffer:
         return states, pol, val, rew, msk, index, torch.ones((rows,), dtype=torch.float64, device=dev)
 
 
+class ReplayWindow:
+    """The off-policy window of a ring: its rows that are committed and tagged with a self-play iteration in [lo, hi].  What a Trainer
+    uses of a ReplayBuffer, on those rows only; the minibatch draws share the ring's draw count."""
+
+    def __init__(self, ring: ReplayBuffer, lo: int, hi: int):
+        self.ring, self.lo, self.hi = ring, int(lo), int(hi)
+        if self.lo > self.hi:
+            raise ValueError(f"window [{lo}, {hi}]: lo > hi")
+
+    def mask(self):
+        r = self.ring
+        return (r.flags == COMMITTED) & (r.iter >= self.lo) & (r.iter <= self.hi)
+
+    def __len__(self) -> int:
+        """Rows in the window (one read of the device)."""
+        return int(self.mask().sum().item())
+
+    def rows(self):
+        """Device int64 indices of the window's rows, ascending."""
+        return self.ring.torch.nonzero(self.mask()).reshape(-1)
+
+    def sample(self, batch_size: int, num_augmented_samples: int = 0, check_empty: bool = True):
+        """ReplayBuffer.sample drawn from the window's rows."""
+        return self.ring._sample(self.mask(), batch_size, num_augmented_samples, check_empty,
+                                 f"no committed sample of self-play iterations {self.lo} .. {self.hi} is in the ring")
+
+    def prioritized(self, batch_size: int = 32, alpha: float = 0.75, beta0: float = 0.5, num_epochs: int = 3) -> "PrioritizedReplay":
+        """ReplayBuffer.prioritized over the window's rows (ipp_replay_priority_reset_window): every other row has no mass."""
+        return PrioritizedReplay(self.ring, batch_size, alpha, beta0, num_epochs, window=(self.lo, self.hi))
+
+
 class PrioritizedReplay:
     """PrioritizedExperienceReplayBuffer (replay_buffers.py:104-141) on the ring of a ReplayBuffer: rows drawn in proportion to
     priority ** alpha, importance-sampling weights (P L) ** -beta over their maximum, priorities written back by update(), beta raised by
@@ -286,7 +410,9 @@ class PrioritizedReplay:
     committed later are not drawn (the reference's file list is fixed too) and a row that a later record re-opens drops out.  The
     minibatch draws share the ring's draw count with ReplayBuffer.sample.  After construction nothing here reads the device from the host."""
 
-    def __init__(self, ring: ReplayBuffer, batch_size: int = 32, alpha: float = 0.75, beta0: float = 0.5, num_epochs: int = 3):
+    def __init__(self, ring: ReplayBuffer, batch_size: int = 32, alpha: float = 0.75, beta0: float = 0.5, num_epochs: int = 3,
+                 window=None):
+        """window: (lo, hi) restricts the sampled set to the committed rows of those self-play iterations (ReplayBuffer.window)."""
         torch = self.torch = ring.torch
         self.ring = ring
         self.alpha, self.beta0, self.beta = float(alpha), float(beta0), float(beta0)
@@ -299,7 +425,11 @@ class PrioritizedReplay:
         self._cum = torch.empty((cap,), dtype=torch.float64, device=dev)
         self._scratch = torch.empty(((cap + _ffi.IPP_REPLAY_SCAN_TILE - 1) // _ffi.IPP_REPLAY_SCAN_TILE,), dtype=torch.float64, device=dev)
         count = torch.zeros((1,), dtype=torch.int64, device=dev)
-        _ffi.check(own._lib.ipp_replay_priority_reset(C.byref(own._sp), self.priorities.data_ptr(), count.data_ptr(), own.env.engine.stream))
+        if window is None:
+            _ffi.check(own._lib.ipp_replay_priority_reset(C.byref(own._sp), self.priorities.data_ptr(), count.data_ptr(), own.env.engine.stream))
+        else:
+            _ffi.check(own._lib.ipp_replay_priority_reset_window(C.byref(own._sp), ring.iter.data_ptr(), int(window[0]), int(window[1]),
+                                                                self.priorities.data_ptr(), count.data_ptr(), own.env.engine.stream))
         self.committed = int(count.item())  # (the one read: len(self.data_file_paths))
         if self.committed == 0:
             raise ValueError("the replay buffer holds no committed sample yet (no episode has ended)")
@@ -443,6 +573,7 @@ class SelfPlay:
             setattr(sp, name, t.data_ptr())
         self.t = 0
         self.last = None
+        self._it = None  # the ipp_selfplay_iter of begin_iteration (the learn loop's iterations)
         self.timing = None  # dict phase -> list of (start, end) event pairs while profiling (tools/selfplay_bench.py)
         self.reset()
 
@@ -467,9 +598,9 @@ class SelfPlay:
             ev.record()
             self.timing.setdefault(name, []).append(ev)
 
-    def step(self):
+    def step(self, _iteration: bool = False):
         """One search per env, record, sample the actions, env.step, commit the episodes that ended.  episode_values: the
-        total_episode_value of every env whose episode ended in this step (NaN elsewhere)."""
+        total_episode_value of every env whose episode ended in this step (NaN elsewhere).  (_iteration: step_iteration's commit.)"""
         env, r, B = self.env, self.replay, self.num_envs
         t = self.t
         slot = t % self.slots
@@ -488,7 +619,13 @@ class SelfPlay:
         self._mark("step")
         env.step(self.action)
         self._mark("commit")
-        _ffi.check(self._lib.ipp_selfplay_commit(C.byref(self._sp), int(t), env.engine.stream))
+        if _iteration:
+            _ffi.check(self._lib.ipp_selfplay_commit_iter(C.byref(self._sp), int(t), C.byref(self._it), env.engine.stream))
+            _ffi.check(self._lib.ipp_selfplay_iter_totals(C.byref(self._sp), C.byref(self._it), self._it_totals.data_ptr(), env.engine.stream))
+            self._it_totals_host.copy_(self._it_totals, non_blocking=True)
+            self._it_totals_ev.record()
+        else:
+            _ffi.check(self._lib.ipp_selfplay_commit(C.byref(self._sp), int(t), env.engine.stream))
         self._mark("end")
         self.t += 1
         return self.episode_values
@@ -497,6 +634,58 @@ class SelfPlay:
         for _ in range(int(steps)):
             self.step()
         return self
+
+    # ------------------------------------------------------------------ iterations of the learn loop
+    def begin_iteration(self, iteration: int, episodes_per_env: int):
+        """Start self-play iteration `iteration` (mcts_zero_mission.py:305-340): every env is to end `episodes_per_env` episodes whose
+        rows are tagged with the iteration; the counters start at zero and every env starts a new episode (reset(): running episodes are
+        abandoned, as the reference starts fresh generators per iteration).  The iteration arrays are allocated once."""
+        torch = self.torch
+        iteration, cap = int(iteration), int(episodes_per_env)
+        if iteration < 0 or cap < 1:
+            raise ValueError(f"iteration = {iteration}, episodes_per_env = {cap}: need iteration >= 0 and at least 1 episode per env")
+        if self._it is None:
+            B, dev = self.num_envs, self.device
+            self.iter_episodes = torch.zeros((B,), dtype=torch.int32, device=dev)
+            self.iter_examples = torch.zeros((B,), dtype=torch.int64, device=dev)
+            self.iter_value_sum = torch.zeros((B,), dtype=torch.float64, device=dev)
+            self._it_totals = torch.zeros((4,), dtype=torch.int64, device=dev)  # (the 32-byte record: three int64 and a double)
+            self._it_totals_host = torch.zeros((4,), dtype=torch.int64).pin_memory()
+            self._it_totals_ev = torch.cuda.Event()
+            self._it = _ffi.IppSelfPlayIter(iter_episodes=self.iter_episodes.data_ptr(), r_iter=self.replay.iter.data_ptr(),
+                                            examples=self.iter_examples.data_ptr(), value_sum=self.iter_value_sum.data_ptr())
+        self._it.iteration, self._it.episode_cap = iteration, cap
+        for t in (self.iter_episodes, self.iter_examples, self.iter_value_sum):
+            t.zero_()
+        self.iteration_totals = dict(episodes_kept=0, envs_at_cap=0, examples=0, value_sum=0.0)
+        self.reset()
+
+    def step_iteration(self):
+        """step() of the running iteration: the commit applies the iteration rule (ipp_selfplay_commit_iter) and the iteration's totals
+        come to pinned memory, the step's one small read.  Returns them: dict(episodes_kept, envs_at_cap, examples, value_sum)."""
+        if self._it is None:
+            raise ValueError("no iteration: call begin_iteration(i, episodes_per_env) first")
+        self.step(_iteration=True)
+        self._it_totals_ev.synchronize()
+        rec = self._it_totals_host.numpy()
+        self.iteration_totals = dict(episodes_kept=int(rec[0]), envs_at_cap=int(rec[1]), examples=int(rec[2]),
+                                     value_sum=float(rec[3:4].view(np.float64)[0]))
+        return self.iteration_totals
+
+    def run_iteration(self, iteration: int, episodes_per_env: int, max_steps: Optional[int] = None):
+        """begin_iteration, then step_iteration until every env has ended episodes_per_env episodes.  Past max_steps (default
+        episodes_per_env x (max_episode_steps + 1): an episode takes at most max_episode_steps steps and one more where it ends without
+        a sample) it raises instead of looping.  Returns the totals record as a dict."""
+        self.begin_iteration(iteration, episodes_per_env)
+        limit = int(episodes_per_env) * (self.max_episode_steps + 1) if max_steps is None else int(max_steps)
+        steps = 0
+        while self.iteration_totals["envs_at_cap"] < self.num_envs:
+            if steps >= limit:
+                raise RuntimeError(f"self-play iteration {int(iteration)}: {self.iteration_totals['envs_at_cap']} of {self.num_envs} envs "
+                                   f"have ended {int(episodes_per_env)} episodes after {steps} steps (max_steps = {limit})")
+            self.step_iteration()
+            steps += 1
+        return dict(self.iteration_totals, steps=steps)
 
     def close(self):
         self.env.engine.close()

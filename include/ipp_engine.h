@@ -929,6 +929,61 @@ int ipp_replay_priority_reset_window(const ipp_selfplay* sp, const int32_t* r_it
                                      uint64_t* count, void* stream);
 
 /*
+ * The COMPACT replay ring (csrc/k_replay_compact.h).  The reference writes a sample's input_feature_planes into its pickle
+ * (planning/mcts_zero/episode_generators.py:157-192) and loads them back for a minibatch (replay_buffers.py:48-101); a dense ring row
+ * here is those planes, C N^2 floats.  They are a pure function of the episode's factor columns, of a few scalars per history entry and
+ * of the map mean at record time, and ipp_feature_planes evaluates that function.  A compact row therefore holds the H ipp_plane_entry
+ * records, the mean [N] and the episode it belongs to; the columns of an ended episode are kept once, in a spare slot of the engine, for
+ * all of its rows; the planes are built when a minibatch is drawn.
+ * The engine has the patch layout and at least num_envs (1 + archive_episodes) slots: [0, num_envs) are the envs, slot
+ * num_envs + e E + (p mod E) archives episode p of env e (E = archive_episodes; p counts the episodes of env e that ENDED since the ring
+ * was built: episodes[e], the running episode's tag; it equals the ledger's episode index until a host reset abandons an episode).
+ * Archiving episode p overwrites episode p - E: the rows of env e still tagged p - E lose their flag (are no longer sampleable) and are
+ * counted in `evicted`.  An episode takes at least one self-play step, so with E >= slots the ring's own wrap-around is always first
+ * and nothing is ever evicted; in general E >= slots / (steps of the shortest episode) is enough.
+ * All arrays [dev], owned by the caller.  The calls were added without an ABI bump: nothing existing changes layout.
+ */
+typedef struct ipp_replay_compact {
+    int32_t history;             /* H = ipp_plane_spec.history of the planes                                        */
+    int32_t archive_episodes;    /* E >= 1                                                                            */
+    ipp_plane_entry* r_entries;  /* [S B][H] the row's history, newest first, root_env = the episode's archive slot  */
+    float*    r_mean;            /* [S B][N] the env's mean when the row was recorded (the mask of all its entries)   */
+    int64_t*  r_episode;         /* [S B]    episode tag of the row                                                   */
+    int64_t*  episodes;          /* [B]      episodes of env e archived so far = tag of its running episode           */
+    int32_t*  last_rank;         /* [B]      rank of env e at its last record                                         */
+    uint64_t* evicted;           /* [1]      rows that lost their flag to a reused archive slot                       */
+} ipp_replay_compact;
+
+/*
+ * Before the search of self-play step `step` (where the dense ring takes its planes): per env e the H records of `entries` ([dev] [B][H],
+ * the env's history with entry 0 = its current state at rank -1) into row (step mod S) B + e, with entry 0's rank made explicit (the
+ * slot's rank now) and the slot of every valid entry replaced by the archive slot of the running episode; the env's current mean; the
+ * tag; last_rank[e].  Refused (-1): an engine without patch layout or with fewer than B (1 + E) slots, history outside [1, 64], E < 1,
+ * a NULL array, step < 0.
+ */
+int ipp_replay_record_compact(void* engine, const ipp_selfplay* sp, const ipp_replay_compact* rc, int64_t step,
+                              const ipp_plane_entry* entries, void* stream);
+/*
+ * After the budget step and BEFORE ipp_selfplay_commit[_iter], on the stream of the step: for every env whose episode ended in the step
+ * (done[e], or forced[e]: a root without a policy), read on the device, the columns [0, last_rank[e]) of the env slot with their spans
+ * and rectangles and the slot's prior pair go to the episode's archive slot, whose rank becomes last_rank[e] + 1: every sample of the
+ * episode is a strict prefix of it and takes the densified diagonal of its own columns.  The step has already reset the env: a reset
+ * rewrites mean, diagonal, rank and prior and leaves the column storage as it is, and the step's own columns lie behind last_rank[e].
+ * Then the eviction (above) and episodes[e] += 1.  Envs whose episode goes on cost an exit per workgroup.  Refusals as above.
+ */
+int ipp_selfplay_archive(void* engine, const ipp_selfplay* sp, const ipp_replay_compact* rc, void* stream);
+/*
+ * The planes of a minibatch drawn with channels = 0 (ipp_replay_gather: index, offsets; ipp_replay_gather_rows: copies = 1, offsets
+ * NULL): states [dev] [n copies][C][N][N].  Rows [0, n): one ipp_feature_planes call on the entries and means of ring rows index[0 .. n)
+ * (a row outside the ring, such as -1: NaN planes); rows c n + i, c >= 1: states[i] shifted by offsets[c] = (i, j), out[y][x] =
+ * in[clamp(y + i - 4)][clamp(x + j - 4)].  Only rows whose episode ended (committed rows) have an archive to read.  ent_scratch [dev]
+ * n H records, mean_scratch [dev] n N floats.  Refusals as above, and what ipp_feature_planes refuses.
+ */
+int ipp_replay_compact_planes(void* engine, const ipp_selfplay* sp, const ipp_replay_compact* rc, const ipp_plane_spec* spec /*[host]*/,
+                              int32_t n, int32_t copies, const int64_t* index, const int32_t* offsets, ipp_plane_entry* ent_scratch,
+                              float* mean_scratch, float* states, void* stream);
+
+/*
  * Playing with a trained network (csrc/k_play.h): the decision of the deployment planner, MCTSZeroMission.replan,
  * planning/mcts_zero/mcts_zero_mission.py:504-523 (`workers` root-parallel searches per decision, their policies summed, normalised,
  * arg-max), and the game bookkeeping of the arena gate, planning/mcts_zero/arenas.py:25-56, for every env of a budget-mode batch at once.

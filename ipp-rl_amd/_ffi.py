@@ -131,6 +131,14 @@ class IppSelfPlayIter(C.Structure):
     ]
 
 
+class IppReplayCompact(C.Structure):
+    """ipp_replay_compact (include/ipp_engine.h): the compact replay ring's rows and per-env archive bookkeeping, [dev] pointers."""
+    _fields_ = [
+        ("history", C.c_int32), ("archive_episodes", C.c_int32),
+        ("r_entries", _P), ("r_mean", _P), ("r_episode", _P), ("episodes", _P), ("last_rank", _P), ("evicted", _P),
+    ]
+
+
 class IppIterTotals(C.Structure):
     """The 32-byte record of ipp_selfplay_iter_totals."""
     _fields_ = [("episodes_kept", C.c_int64), ("envs_at_cap", C.c_int64), ("examples", C.c_int64), ("value_sum", C.c_double)]
@@ -285,6 +293,11 @@ PROTOTYPES = {
     "ipp_selfplay_commit_iter": (C.c_int, [C.POINTER(IppSelfPlay), C.c_int64, C.POINTER(IppSelfPlayIter), _P]),
     "ipp_selfplay_iter_totals": (C.c_int, [C.POINTER(IppSelfPlay), C.POINTER(IppSelfPlayIter), _P, _P]),
     "ipp_replay_priority_reset_window": (C.c_int, [C.POINTER(IppSelfPlay), _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    # (the compact replay ring, csrc/k_replay_compact.h: added without an ABI bump as well)
+    "ipp_replay_record_compact": (C.c_int, [_P, C.POINTER(IppSelfPlay), C.POINTER(IppReplayCompact), C.c_int64, _P, _P]),
+    "ipp_selfplay_archive": (C.c_int, [_P, C.POINTER(IppSelfPlay), C.POINTER(IppReplayCompact), _P]),
+    "ipp_replay_compact_planes": (C.c_int, [_P, C.POINTER(IppSelfPlay), C.POINTER(IppReplayCompact), C.POINTER(IppPlaneSpec), C.c_int32,
+                                            C.c_int32, _P, _P, _P, _P, _P, _P]),
     # (the deployment planner's and the arena's calls, csrc/k_play.h: added without an ABI bump, nothing existing changes layout)
     "ipp_play_pick": (C.c_int, [C.POINTER(IppPlay), _P, _P, _P, _P]),
     "ipp_play_tally": (C.c_int, [C.POINTER(IppPlay), _P]),

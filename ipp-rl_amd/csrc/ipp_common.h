@@ -263,6 +263,10 @@ __device__ __forceinline__ double budget_start(const Ledger& L, int env, long lo
 // One wave resets env `env` (mapping/mappings.py:235-240,259-261: mean 0.5, P = prior; factor state: rank 0) and
 // installs ground truth field k.  The caller guarantees that every earlier store / atomic to the env's planes
 // has completed.
+// INVARIANT the compact replay ring rests on (k_replay_compact.h, k_rc_archive): a reset rewrites mean, diag, the ground-truth
+// plane or gt_slot, rank, prior and prev, and NOTHING of the column storage (cov, colspan, colrect).  The step that ended the episode
+// appended its columns behind the rank it found, so after a step with a reset the columns [0, pre-step rank) of the ended episode
+// are still intact and can be archived behind the launch (tests/test_hip_replay_compact.py pins it bit for bit).
 __device__ __forceinline__ void wave_reset_env(const View& v, const AutoReset& ar, int env, int k, int lane) {
     // (prior of the new episode like k_reset_small: shuffle_prior_cov scales, mappings.py:238-240; a length scale the column
     // window was not sized for poisons the env instead of losing accuracy silently)

@@ -1476,6 +1476,15 @@ int ipp::tree_engine(void* engine, TreeEngine* out) {
     return 0;
 }
 
+int ipp::factor_slots(void* engine, FactorSlots* out) {
+    const Engine* e = as_engine(engine);
+    if (!e) return fail(-1, "null engine");
+    const View& v = e->v;
+    *out = FactorSlots{e->device, v.cap, v.rank_cap, v.N, v.Npad, v.pstride, e->patch && v.mode == IPP_FACTOR, v.cov_slot,
+                       v.cov, v.colspan, v.colrect, v.rank, v.prior, v.mean};
+    return 0;
+}
+
 int ipp::tree_step(void* engine, const int32_t* root_ids, const int32_t* path_ids, const int32_t* new_ids, int32_t n, const double* action,
                    const double* prev_action, uint32_t flags, float* reward, int32_t* status, void* stream, const int32_t* n_dev,
                    const TreeEdgeOut* edge_out) {

@@ -20,6 +20,15 @@ struct TreeEngine {  // read at every call (ipp_set_uav changes vmax / amax)
 };
 int tree_engine(void* engine, TreeEngine* out);  // (null engine: "null engine")
 
+// The factor storage of an engine's env slots as the compact replay ring's calls see it (k_replay_compact.h): the slabs of View
+struct FactorSlots {
+    int device, cap, rank_cap, N, Npad, pstride;
+    bool patch;
+    uint64_t cov_slot;  // floats per slot
+    float* cov; int* colspan; int* colrect; int* rank; double* prior; const float* mean;
+};
+int factor_slots(void* engine, FactorSlots* out);  // (null engine: "null engine")
+
 // ipp_tree_step + the search driver's extras: the item count on the device (n_dev), the edge numerators written by the patch kernel
 // itself (edge_out: ipp_common.h); either may be NULL
 struct TreeEdgeOut;

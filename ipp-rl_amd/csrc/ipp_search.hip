@@ -8,6 +8,7 @@
 #include "k_mcts.h"
 #include "k_selfplay.h"
 #include "k_replay_per.h"
+#include "k_replay_compact.h"
 #include "k_learn.h"
 #include "k_play.h"
 #include "k_rollout.h"
@@ -329,6 +330,77 @@ int ipp_replay_priority_reset_window(const ipp_selfplay* sp, const int32_t* r_it
     hipLaunchKernelGGL(k_per_reset_win, dim3(blocks), dim3(kPerThreads), 0, s, sp->r_flags, r_iter, (int)lo, (int)hi, cap,
                        reinterpret_cast<const unsigned long long*>(count), priority);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- the compact replay ring (k_replay_compact.h)
+static int replay_compact_check(void* engine, const ipp_selfplay* sp, const ipp_replay_compact* rc, FactorSlots* fs) {
+    if (int err = selfplay_check(sp)) return err;
+    if (!rc) return fail(-1, "null argument");
+    if (rc->history < 1 || rc->history > 64) return fail(-1, "ipp_replay_compact: history = %d outside [1, 64]", rc->history);
+    if (rc->archive_episodes < 1) return fail(-1, "ipp_replay_compact: archive_episodes = %d < 1", rc->archive_episodes);
+    if (!rc->r_entries || !rc->r_mean || !rc->r_episode || !rc->episodes || !rc->last_rank || !rc->evicted)
+        return fail(-1, "ipp_replay_compact: null device pointer");
+    if (int err = factor_slots(engine, fs)) return err;
+    if (!fs->patch) return fail(-1, "the compact replay ring needs the patch-layout windowed factor engine (ipp_info.patch_layout == 1)");
+    const long long need = (long long)sp->num_envs * (1 + (long long)rc->archive_episodes);
+    if (need > fs->cap)
+        return fail(-1, "the compact replay ring needs num_envs (1 + archive_episodes) = %lld engine slots, the engine has %d", need, fs->cap);
+    if (fs->device != sp->device) return fail(-1, "engine on device %d, ipp_selfplay on device %d", fs->device, sp->device);
+    return 0;
+}
+
+int ipp_replay_record_compact(void* engine, const ipp_selfplay* sp, const ipp_replay_compact* rc, int64_t step,
+                              const ipp_plane_entry* entries, void* stream) {
+    FactorSlots fs;
+    if (int err = replay_compact_check(engine, sp, rc, &fs)) return err;
+    if (step < 0) return fail(-1, "step = %lld < 0", (long long)step);
+    if (!entries) return fail(-1, "null argument");
+    HIP_TRY(hipSetDevice(sp->device));
+    hipLaunchKernelGGL(k_rc_record, dim3(sp->num_envs), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *sp, *rc, fs, (long long)step,
+                       entries);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ipp_selfplay_archive(void* engine, const ipp_selfplay* sp, const ipp_replay_compact* rc, void* stream) {
+    FactorSlots fs;
+    if (int err = replay_compact_check(engine, sp, rc, &fs)) return err;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(sp->device));
+    // (chunks of a slot's columns as in ipp_fork: 1024 float4 per workgroup and pass, at most 64 workgroups per env)
+    const uint64_t n4 = (uint64_t)fs.rank_cap * (uint64_t)fs.pstride / 4;
+    const int chunks = (int)std::max<uint64_t>(1, std::min<uint64_t>(64, (n4 + 1023) / 1024));
+    hipLaunchKernelGGL(k_rc_archive, dim3(chunks, sp->num_envs), dim3(256), 0, s, *sp, *rc, fs);
+    hipLaunchKernelGGL(k_rc_evict, dim3(sp->num_envs), dim3(kWave), 0, s, *sp, *rc);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ipp_replay_compact_planes(void* engine, const ipp_selfplay* sp, const ipp_replay_compact* rc, const ipp_plane_spec* spec, int32_t n,
+                              int32_t copies, const int64_t* index, const int32_t* offsets, ipp_plane_entry* ent_scratch,
+                              float* mean_scratch, float* states, void* stream) {
+    FactorSlots fs;
+    if (int err = replay_compact_check(engine, sp, rc, &fs)) return err;
+    if (!spec || !index || !ent_scratch || !mean_scratch || !states) return fail(-1, "null argument");
+    if (spec->history != rc->history) return fail(-1, "spec.history = %d, ipp_replay_compact.history = %d", spec->history, rc->history);
+    if (n < 1 || copies < 1) return fail(-1, "n = %d, copies = %d: need both >= 1", n, copies);
+    if (copies > 1 && !offsets) return fail(-1, "augmented copies need ipp_replay_gather's offsets");
+    const int C = (spec->use_fov ? 3 : 5) * spec->history + ((spec->use_costs && !spec->use_fov) ? 1 : 0);
+    const long long blocks = (long long)n * (copies - 1) * C;
+    if (blocks > INT32_MAX) return fail(-1, "%lld blocks: minibatch too large", blocks);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(sp->device));
+    hipLaunchKernelGGL(k_rc_entries, dim3(n), dim3(256), 0, s, *rc, (long long)sp->num_envs * sp->slots, fs.N, (int)n, index, ent_scratch,
+                       mean_scratch);
+    HIP_TRY(hipGetLastError());
+    if (int err = ipp_feature_planes(engine, spec, ent_scratch, n, nullptr, mean_scratch, states, stream)) return err;
+    if (copies > 1) {
+        SpGather g{};
+        g.n = n; g.copies = copies; g.C = C; g.side = fs.N; g.planes = states; g.states = states;
+        hipLaunchKernelGGL(k_rc_crop, dim3((unsigned)blocks), dim3(256), 0, s, g, offsets);
+        HIP_TRY(hipGetLastError());
+    }
     return 0;
 }
 

@@ -84,6 +84,30 @@ def prior_kind(nu) -> int:
     return kind
 
 
+PATCH_MAX_RANK, PATCH_MAX_WINDOW = 512, 25  # csrc/k_step_patch.h kPatchMaxRank; csrc/ipp_engine.hip patch_layout
+
+
+def patch_layout_possible(cfg: "EngineConfig", state: str = "factor", window_rows: int = -1, fixed_prior: bool = True,
+                          rank_cap: int = 360, tile_threads: int = 0) -> bool:
+    """The rules of csrc/ipp_engine.hip's patch_layout that need no device: whether an engine of this grid, window and rank_cap CAN
+    store its factor columns as patches (ipp_info.patch_layout == 1).  False is final; True is confirmed by the engine's info once it
+    is built (the A/B switches and the exactness check of the patch units can still select the band-tile kernels).  window_rows < 0:
+    the smallest window the engine accepts for the prior (ipp_min_window_rows_prior: a host call)."""
+    if state != "factor" or tile_threads != 0:
+        return False
+    rows = int(window_rows)
+    if rows < 0:
+        c = _ffi.IppConfig()
+        c.x_dim, c.y_dim, c.resolution = cfg.x_dim, cfg.y_dim, cfg.resolution
+        c.signal_variance, c.length_scale, c.fixed_prior = cfg.signal_variance, cfg.length_scale, 1 if fixed_prior else 0
+        out = C.c_int32(0)
+        _ffi.check(_ffi.load().ipp_min_window_rows_prior(C.byref(c), prior_kind(getattr(cfg, "nu", 1.5)), C.byref(out)))
+        rows = int(out.value)
+    if rows <= 0 or rows > PATCH_MAX_WINDOW or int(rank_cap) > PATCH_MAX_RANK:
+        return False
+    return cfg.x_dim % 2 == 0 and cfg.x_dim <= 256 and cfg.y_dim <= 256 and cfg.x_dim > 2 * rows + 13
+
+
 def _torch():
     import torch
 

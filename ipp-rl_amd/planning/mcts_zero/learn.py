@@ -92,7 +92,8 @@ class Learner:
         ends per iteration (default ceil(num_episodes x num_workers / num_envs): at least the reference's episodes per iteration).
         arena_envs: envs of the gate's arena (default gcd(num_arena_games, num_envs)).  net_max_batch: leaves one forward of a device
         network takes (default max(num_envs, arena_envs) x sims_in_flight).  selfplay_kwargs go to SelfPlay (capacity: the ring has to
-        hold the rows of a whole off-policy window, see INTEGRATION.md "Learn loop"); sims_in_flight, tie_break and groups go to the
+        hold the rows of a whole off-policy window, see INTEGRATION.md "Learn loop"; planes="compact" and archive_episodes: the compact
+        ring, whose rows are a few KB, so that such a window fits beside thousands of envs); sims_in_flight, tie_break and groups go to the
         arena too."""
         self.episodes_per_env, self.arena_envs = check_args(hyper_params, num_envs, episodes_per_env, arena_envs)
         import torch

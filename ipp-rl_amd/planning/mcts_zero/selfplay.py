@@ -33,6 +33,13 @@ the iteration in ReplayBuffer.iter, later episodes are played out and dropped --
 (ipp_selfplay_iter_totals) from pinned memory, the step's one new read.  ReplayBuffer.window(lo, hi) serves a Trainer the rows of
 iterations lo .. hi (planning/mcts_zero/learn.py).
 
+The compact ring (planes="compact"; csrc/k_replay_compact.h): a row's planes are a function of its episode's factor columns, a few scalars
+per history entry and the mean at record time, so the row keeps those (ipp_replay_record_compact, where `planes` is above), an ended
+episode's columns are copied once into a spare engine slot between `step` and `commit` (ipp_selfplay_archive: the predicate is read on the
+device) and a minibatch builds the planes of its rows (ipp_replay_compact_planes).  Same draws, same seven outputs; bit-identical to the
+dense ring with interval_factor = 0, and with interval_factor != 0 the newest state's mask takes the densified diagonal of its column
+prefix where the dense ring takes the slot's incrementally stored one (two fp32 evaluations of the same P_ii).
+
 Divergences from the reference (INTEGRATION.md "Batched self-play"): a temperature-0 sample stores the real valid-action mask where the
 reference stores the visit counts (mcts.py:138); no tree reuse between steps, no per-episode shuffled priors; the draws are counter-based,
 not NumPy's global stream.
@@ -276,14 +283,58 @@ def check_args(hyper_params: Dict, meta_data: Dict, num_envs: int, capacity: Opt
     return S, steps
 
 
+def check_replay_mode(planes, archive_episodes, slots: int) -> int:
+    """The ring's plane mode: True (dense planes), False (none) or "compact" (entries + mean per row, the planes built when a minibatch
+    is drawn).  Returns E, the episodes archived per env in compact mode (archive_episodes; None: the ring's step slots S, with which
+    nothing is ever evicted), 0 in the other modes.  Refused before anything touches a device."""
+    if not any(planes is m for m in (True, False)) and planes != "compact":
+        raise ValueError(f"planes = {planes!r}: True, False or 'compact'")
+    if archive_episodes is not None and int(archive_episodes) < 1:
+        raise ValueError(f"archive_episodes = {archive_episodes} < 1")
+    if planes != "compact":
+        return 0
+    return int(slots) if archive_episodes is None else int(archive_episodes)
+
+
+def archive_slot(num_envs: int, archive_episodes: int, env, episode):
+    """Engine slot that archives episode `episode` (the count of the env's episodes that ended before it) of env `env`: the spare
+    slots follow the env slots, E per env (ipp_replay_compact, include/ipp_engine.h)."""
+    return int(num_envs) + np.asarray(env, dtype=np.int64) * int(archive_episodes) + np.asarray(episode, dtype=np.int64) % int(archive_episodes)
+
+
+def eviction_host(trace, slots: int, archive_episodes: int):
+    """ipp_selfplay_archive's eviction and the ring's committed rows on a host trace of ONE env: trace[t] = (episode tag of the env's
+    running episode at step t, recorded: the step left a sample, ended: the episode ended in step t).  Row t mod S takes the sample of
+    step t (flag pending, tag = the episode; a step without a sample clears the row).  When episode p ends, the rows still flagged and
+    tagged p - E lose their flag and are counted, then the rows of episode p become committed.  Returns (flags [S] uint8, tags [S]
+    int64, evicted)."""
+    S, E = int(slots), int(archive_episodes)
+    flags, tags = np.zeros(S, dtype=np.uint8), np.full(S, -1, dtype=np.int64)
+    evicted = 0
+    for t, (p, recorded, ended) in enumerate(trace):
+        s = t % S
+        flags[s] = PENDING if recorded else 0
+        tags[s] = int(p)
+        if ended:
+            old = (flags != 0) & (tags == int(p) - E)
+            evicted += int(old.sum())
+            flags[old] = 0
+            flags[(flags == PENDING) & (tags == int(p))] = COMMITTED
+    return flags, tags, evicted
+
+
 # ---------------------------------------------------------------------------------------------------- replay buffer
 class ReplayBuffer:
     """The samples of a SelfPlay batch in device memory: S x B rows of planes [C, N, N] fp32 (channels > 0), sparse policy (fp32 on the
     kmax slots of the root's valid set), valid set (int32, -1 padded), value target, reward (fp64) and a flag (1 pending, 2 committed).
-    sample() draws from the committed rows only."""
+    sample() draws from the committed rows only.
+    compact=(H, E): no planes tensor (self.planes is None).  A row keeps its H history entries (ipp_plane_entry, 72 bytes each), the
+    env's mean at record time [N] fp32 and its episode tag; the columns of an ended episode live once in a spare engine slot (E per
+    env), and sample() builds the planes of the drawn rows with one ipp_feature_planes call (ipp_replay_compact_planes).  `evicted`
+    counts the rows that lost their flag because their episode's archive slot was reused (never with E >= S)."""
 
     def __init__(self, owner: "SelfPlay", slots: int, num_envs: int, kmax: int, num_actions: int, channels: int, side: int, seed: int,
-                 device):
+                 device, compact=None):
         import torch
 
         self.torch = torch
@@ -292,7 +343,22 @@ class ReplayBuffer:
         cap = self.capacity = self.slots * self.num_envs
         e = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)  # noqa: E731
         self.planes = None
-        if self.channels:
+        self.compact = None
+        if compact is not None:
+            from ...feature_planes import empty_entries
+
+            H, E = int(compact[0]), int(compact[1])
+            self.history, self.archive_episodes = H, E
+            self.entries = empty_entries(cap, H, device)                      # [cap, H, 18] int32 = ipp_plane_entry records
+            self.mean = e((cap, self.side), torch.float32)
+            self.episode_tag = torch.full((cap,), -1, dtype=torch.int64, device=device)
+            self.episodes = e((self.num_envs,), torch.int64)                  # episodes of env e archived so far = its running episode's tag
+            self.last_rank = e((self.num_envs,), torch.int32)
+            self._evicted = e((1,), torch.int64)
+            self.compact = _ffi.IppReplayCompact(history=H, archive_episodes=E, r_entries=self.entries.data_ptr(), r_mean=self.mean.data_ptr(),
+                                                 r_episode=self.episode_tag.data_ptr(), episodes=self.episodes.data_ptr(),
+                                                 last_rank=self.last_rank.data_ptr(), evicted=self._evicted.data_ptr())
+        elif self.channels:
             need = cap * self.channels * self.side * self.side * 4
             total = torch.cuda.get_device_properties(device).total_memory
             if need > total // 2:
@@ -313,6 +379,50 @@ class ReplayBuffer:
     def __len__(self) -> int:
         """Committed rows (reads the device)."""
         return int((self.flags == COMMITTED).sum().item())
+
+    def nbytes(self) -> int:
+        """Device bytes of the ring, in every mode: the rows' arrays (planes or entries + mean + tag; policy, valid set, value, reward,
+        flag, iteration) and, in compact mode, the per-env archive bookkeeping.  The archived columns live in the engine's spare slots."""
+        ts = [self.planes, self.policy, self.idx, self.value, self.reward, self.flags, self.iter]
+        if self.compact is not None:
+            ts += [self.entries, self.mean, self.episode_tag, self.episodes, self.last_rank, self._evicted]
+        return int(sum(t.numel() * t.element_size() for t in ts if t is not None))
+
+    @property
+    def evicted(self) -> int:
+        """Rows that lost their flag because the archive slot of their episode was reused (compact mode; reads the device)."""
+        return int(self._evicted.item()) if self.compact is not None else 0
+
+    def _compact_planes(self, n: int, copies: int, index, offsets, states):
+        """states [n copies, C, N, N] of a minibatch drawn with channels = 0 (ipp_replay_compact_planes)."""
+        torch, own = self.torch, self._owner
+        dev = self.flags.device
+        ent = torch.empty((n, self.history, self.entries.shape[2]), dtype=torch.int32, device=dev)
+        mean = torch.empty((n, self.side), dtype=torch.float32, device=dev)
+        cs = own.spec.to_c()
+        _ffi.check(own._lib.ipp_replay_compact_planes(own.env.engine._h, C.byref(own._sp), C.byref(self.compact), C.byref(cs), n, copies,
+                                                      index.data_ptr(), offsets.data_ptr() if offsets is not None else None,
+                                                      ent.data_ptr(), mean.data_ptr(), states.data_ptr(), own.env.engine.stream))
+
+    def gather_rows(self, rows):
+        """(states, policies, values, rewards, valid_actions_msk) of the given ring rows, unshifted (ipp_replay_gather_rows; a row outside
+        the ring: NaN).  In compact mode only committed rows have planes: a running episode has no archive yet."""
+        torch, own = self.torch, self._owner
+        dev = self.flags.device
+        index = torch.as_tensor(rows, device=dev).to(torch.int64).reshape(-1).contiguous()
+        n = int(index.numel())
+        states = torch.empty((n, self.channels, self.side, self.side), dtype=torch.float32, device=dev) if self.channels else None
+        pol = torch.empty((n, self.num_actions), dtype=torch.float32, device=dev)
+        msk = torch.empty((n, self.num_actions), dtype=torch.uint8, device=dev)
+        val = torch.empty((n,), dtype=torch.float64, device=dev)
+        rew = torch.empty((n,), dtype=torch.float64, device=dev)
+        gc = self.channels if self.planes is not None else 0
+        _ffi.check(own._lib.ipp_replay_gather_rows(C.byref(own._sp), n, gc, self.side, self.planes.data_ptr() if gc else None,
+                                                   index.data_ptr(), states.data_ptr() if gc else None, pol.data_ptr(), msk.data_ptr(),
+                                                   val.data_ptr(), rew.data_ptr(), own.env.engine.stream))
+        if self.compact is not None:
+            self._compact_planes(n, 1, index, None, states)
+        return states, pol, val, rew, msk
 
     def committed_rows(self):
         """Device int64 indices of the committed rows, ascending."""
@@ -359,11 +469,14 @@ class ReplayBuffer:
         if self.timing is not None:  # (events around the gather kernel alone: tools/selfplay_bench.py)
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
             ev[0].record()
-        _ffi.check(own._lib.ipp_replay_gather(C.byref(own._sp), n, copies, self.channels, self.side,
-                                              self.planes.data_ptr() if self.channels else None, cum.data_ptr(), C.c_uint64(self.seed),
-                                              C.c_uint64(REPLAY_STREAM + self.draws), states.data_ptr() if states is not None else None,
+        gc = self.channels if self.planes is not None else 0  # (compact: the row draw alone, then the planes of the drawn rows)
+        _ffi.check(own._lib.ipp_replay_gather(C.byref(own._sp), n, copies, gc, self.side,
+                                              self.planes.data_ptr() if gc else None, cum.data_ptr(), C.c_uint64(self.seed),
+                                              C.c_uint64(REPLAY_STREAM + self.draws), states.data_ptr() if gc else None,
                                               pol.data_ptr(), msk.data_ptr(), val.data_ptr(), rew.data_ptr(), index.data_ptr(), offs.data_ptr(),
                                               own.env.engine.stream))
+        if self.compact is not None:
+            self._compact_planes(n, copies, index, offs, states)
         if self.timing is not None:
             ev[1].record()
             self.timing.append(ev)
@@ -466,9 +579,12 @@ class PrioritizedReplay:
                                                 weights.data_ptr(), st))
         if self.timing is not None:
             ev[1].record()
-        _ffi.check(own._lib.ipp_replay_gather_rows(sp, n, r.channels, r.side, r.planes.data_ptr() if r.channels else None, index.data_ptr(),
-                                                   states.data_ptr() if states is not None else None, pol.data_ptr(), msk.data_ptr(),
+        gc = r.channels if r.planes is not None else 0
+        _ffi.check(own._lib.ipp_replay_gather_rows(sp, n, gc, r.side, r.planes.data_ptr() if gc else None, index.data_ptr(),
+                                                   states.data_ptr() if gc else None, pol.data_ptr(), msk.data_ptr(),
                                                    val.data_ptr(), rew.data_ptr(), st))
+        if r.compact is not None:
+            r._compact_planes(n, 1, index, None, states)
         if self.timing is not None:
             ev[2].record()
             self.timing.append(ev)
@@ -497,15 +613,30 @@ class PrioritizedReplay:
 class SelfPlay:
     def __init__(self, cfg, num_envs: int, hyper_params: Dict, meta_data: Dict, infer: Optional[Callable] = None,
                  capacity: Optional[int] = None, seed: int = 0, env_id_offset: int = 0, random_init_action: bool = True,
-                 planes: bool = True, sims_in_flight: int = 4, tie_break: str = "first", groups: int = 2, device: str = "cuda:0",
-                 **env_kwargs):
+                 planes=True, sims_in_flight: int = 4, tie_break: str = "first", groups: int = 2, device: str = "cuda:0",
+                 archive_episodes: Optional[int] = None, **env_kwargs):
         """cfg: EngineConfig; hyper_params / meta_data: the reference's dictionaries (config/example.yaml: gamma, puct_*, dirichlet_*,
         num_mcts_simulations, temperature_scale / _threshold, input_history_length, use_fov_input, use_action_costs_input, shuffle_budget;
         initial_budget, max_episode_steps, episode_horizon, min / max_altitude, altitude_spacing, uav_specifications, scenario_info).
         infer: DeviceMCTS's network callback (None: uniform priors, value 0); with a network the leaves' planes come along.
         capacity: ring rows (a multiple of num_envs, at least (max_episode_steps + 1) num_envs; default the minimum).
-        planes=False keeps no planes in the ring (large grids: a 50x50 plane is 25 MB per channel).  env_kwargs go to VecIPPEnv."""
+        planes=False keeps no planes in the ring (large grids: a 50x50 plane is 25 MB per channel).  planes="compact" keeps, per row,
+        the history entries, the mean and the episode tag (a few KB) and, per ended episode, one copy of its factor columns in a spare
+        engine slot; the planes are built when a minibatch is drawn (ReplayBuffer).  archive_episodes = E: archive slots per env
+        (spare_slots = num_envs E go to the env); None: the ring's step slots S, with which nothing is evicted; a smaller E evicts
+        the rows of episode p - E when episode p ends: E >= S / (steps of the shortest episode expected) avoids it.
+        env_kwargs go to VecIPPEnv."""
         S, steps = check_args(hyper_params, meta_data, num_envs, capacity)
+        E = check_replay_mode(planes, archive_episodes, S)
+        if E:
+            from ...engine import patch_layout_possible
+
+            if not patch_layout_possible(cfg, env_kwargs.get("state", "factor"), env_kwargs.get("window_rows", -1), True,
+                                         env_kwargs.get("rank_cap", 9 * (steps + int(meta_data["episode_horizon"]) + 2)),
+                                         env_kwargs.get("tile_threads", 0)):
+                raise ValueError("planes='compact' archives episodes as patch-layout factor slots (ipp_info.patch_layout == 1): this grid, "
+                                 "window or rank_cap cannot have it")
+            env_kwargs["spare_slots"] = int(num_envs) * E
         import torch
 
         from ...feature_planes import PlaneSpec
@@ -533,8 +664,10 @@ class SelfPlay:
         env = self.env
         self.device = env.device
         self.spec = PlaneSpec.from_params(hp, md, adaptive=env.adaptive, use_flight_time=env.use_flight_time)
+        # (the search divides the engine's tree nodes among its SLOTS by default; with spare slots the roots are the envs alone)
+        dev_per_root = max(1, min(2 * sims + 2 * W + 8, int(env.engine._c.node_capacity) // B)) if env.spare_slots else None
         self.mcts = DeviceMCTS(env.engine, hp, md, infer, sims_in_flight=W, tie_break=tie_break, seed=seed, groups=groups,
-                               feature_planes=infer is not None)
+                               feature_planes=infer is not None, dev_per_root=dev_per_root)
         self.mcts._key_base = env.env_id_offset  # (the search's counter-based draws keyed on the global env id too)
         self.infer = infer
         geo = self.mcts._geometry(torch, self.device)
@@ -552,7 +685,7 @@ class SelfPlay:
         self._temps = ([scale] if need_pos else []) + ([1.0] if need_zero and not (need_pos and scale == 1.0) else [])
         self._t_index = (0, len(self._temps) - 1)  # (policy_t, policy_1) among the read-outs
         self.replay = ReplayBuffer(self, S, B, self.kmax, self.num_actions, self.spec.channels if planes else 0, cfg.n_cells,
-                                   seed, self.device)
+                                   seed, self.device, compact=(H, E) if E else None)
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.device)  # noqa: E731
         self.ep_len, self.forced = z((B,), torch.int32), z((B,), torch.uint8)
         self.tie_u = z((B,), torch.float64)
@@ -606,7 +739,10 @@ class SelfPlay:
         slot = t % self.slots
         self._mark("planes")
         ent = env.history_entries() if (r.channels or self.infer is not None) else None
-        if r.channels:  # (= env.feature_planes(spec, out=...): the same entries feed the search's leaf planes)
+        if r.compact is not None:  # (what the planes are a function of, not the planes)
+            _ffi.check(self._lib.ipp_replay_record_compact(env.engine._h, C.byref(self._sp), C.byref(r.compact), int(t), ent.data_ptr(),
+                                                           env.engine.stream))
+        elif r.channels:  # (= env.feature_planes(spec, out=...): the same entries feed the search's leaf planes)
             env.engine.feature_planes(ent, self.spec, mask_env=ent[:, 0, 0], out=r.planes[slot * B:(slot + 1) * B])
         self._mark("search")
         out = self.mcts.search_device(self._roots, env.prev, env.budget, self._temps, self.tie_u, depth=0,
@@ -618,6 +754,9 @@ class SelfPlay:
                                                  out["ok"].data_ptr(), env.engine.stream))
         self._mark("step")
         env.step(self.action)
+        if r.compact is not None:  # (the ended episodes' columns into their archive slots: behind the step's resets, before the commit)
+            self._mark("archive")
+            _ffi.check(self._lib.ipp_selfplay_archive(env.engine._h, C.byref(self._sp), C.byref(r.compact), env.engine.stream))
         self._mark("commit")
         if _iteration:
             _ffi.check(self._lib.ipp_selfplay_commit_iter(C.byref(self._sp), int(t), C.byref(self._it), env.engine.stream))

@@ -140,7 +140,7 @@ class VecIPPEnv:
                  rank_cap: Optional[int] = None, stagger: bool = False, tile_threads: int = 0,
                  adaptive: bool = True, use_flight_time: bool = True, window_rows: int = 0, fused_reset: bool = True,
                  parts: int = 1, arena=None, budget: Optional[float] = None, shuffle_budget: bool = False, feature_history: int = 0,
-                 node_capacity: int = 0, max_batch: Optional[int] = None):
+                 node_capacity: int = 0, max_batch: Optional[int] = None, spare_slots: int = 0):
         """budget=None: episodes of exactly `episode_steps` steps on a schedule known to the host.  budget=B0: the reference's
         budget-driven episodes (planning/mcts_zero/episode_generators.py:109-150) -- `episode_steps` is max_episode_steps, every env
         carries a device-side ledger (self.budget, self.depth, self.episode, self.done) that the step kernel charges with the action
@@ -148,12 +148,16 @@ class VecIPPEnv:
         the step from the device's refill list (no device->host sync in the loop).  shuffle_budget: start budgets
         floor(U(10, B0)) per env and episode (start_budget).  node_capacity / max_batch: the engine's tree nodes and largest launch
         (IPPEngine), for a search whose roots are the env slots (planning/mcts_zero/selfplay.py); the defaults build no nodes and launches of
-        num_envs items."""
+        num_envs items.  spare_slots=K: the engine gets num_envs + K slots; [0, num_envs) are the envs, the slots above them are never
+        stepped or reset by the env (the compact replay ring archives ended episodes there); K = 0 builds exactly the engine without it."""
         import torch
 
         self.torch = torch
         self.cfg = cfg
         self.num_envs = int(num_envs)
+        self.spare_slots = int(spare_slots)
+        if self.spare_slots < 0:
+            raise ValueError(f"spare_slots = {spare_slots} < 0")
         self.episode_steps = int(episode_steps)
         self.seed = int(seed)
         self.env_id_offset = int(env_id_offset)
@@ -181,9 +185,11 @@ class VecIPPEnv:
         elif shuffle_budget:
             raise ValueError("shuffle_budget needs budget")
         rank_cap = int(rank_cap) if rank_cap else 9 * self.episode_steps
-        self.engine = IPPEngine(cfg, capacity=self.num_envs, state=state, rank_cap=rank_cap, device=device,
+        # (max_batch stays the env batch's: the spare slots are never items of a launch)
+        self.engine = IPPEngine(cfg, capacity=self.num_envs + self.spare_slots, state=state, rank_cap=rank_cap, device=device,
                                 tile_threads=tile_threads, window_rows=window_rows, fixed_prior=not shuffle_prior_cov,
-                                arena=arena, node_capacity=int(node_capacity), max_batch=max_batch)
+                                arena=arena, node_capacity=int(node_capacity),
+                                max_batch=max_batch if (max_batch or not self.spare_slots) else self.num_envs)
         if self.budget_mode and (int(self.engine.info.patch_layout) != 1 or int(self.engine.info.fused_step) != 1):
             self.engine.close()
             raise ValueError("budget mode: patch-layout engines only (windowed factor state, ipp_info.patch_layout == 1)")
@@ -191,7 +197,9 @@ class VecIPPEnv:
         dev = self.engine.device
         self.device = dev
         B = self.num_envs
-        self.prev = torch.tensor(INIT_ACTION, dtype=torch.float64, device=dev).repeat(B, 1)
+        # (the engine's reset takes the waypoints of ALL its slots, [capacity, 3]: the envs' are the leading rows of that tensor)
+        self._prev_slots = torch.tensor(INIT_ACTION, dtype=torch.float64, device=dev).repeat(B + self.spare_slots, 1)
+        self.prev = self._prev_slots[:B]
         self.init_prev = self.prev.clone()
         # stagger: env e starts its first episode at phase e % T so that every batched step sees the
         # stationary mix of ranks 0 .. (T-1)*m (throughput runs); otherwise all envs run in lock step
@@ -370,11 +378,11 @@ class VecIPPEnv:
             white = self._white[:len(sel)]
             if self.field_kind == _ffi.IPP_FIELD_GRF:
                 self.engine.normal_rows(white, self.cfg.n_cells, self.seed, self.GT_STREAM + int(e), row_ids=ids, row_offset=self.env_id_offset)
-                self.engine.reset(env_ids=ids, white_noise=white, prev=self.prev, init_action=INIT_ACTION)
+                self.engine.reset(env_ids=ids, white_noise=white, prev=self._prev_slots, init_action=INIT_ACTION)
             else:
                 self.engine.generate_fields_rows(self.field_kind, len(sel), self.seed, self.GT_STREAM + int(e), white, row_ids=ids,
                                                  row_offset=self.env_id_offset)
-                self.engine.reset(env_ids=ids, gt=white, prev=self.prev, init_action=INIT_ACTION)
+                self.engine.reset(env_ids=ids, gt=white, prev=self._prev_slots, init_action=INIT_ACTION)
             # the next episode's field into the alternate planes: a reset on done flips to it
             self.engine.generate_fields_rows(self.field_kind, len(sel), self.seed, self.GT_STREAM + int(e) + 1, None, row_ids=ids,
                                              row_offset=self.env_id_offset)
@@ -559,7 +567,7 @@ class VecIPPEnv:
                 ih = self._ids_host(ids, env_ids, _phase)
                 prior_scale = self._prior_scale(ih, self.episode[np.asarray(ih, dtype=np.int64)])
         # the reset kernel also returns the UAVs to Mission.init_action (ipp_reset_episode)
-        self.engine.reset(env_ids=ids, prior_scale=prior_scale, gt=gt, white_noise=white_noise, prev=self.prev,
+        self.engine.reset(env_ids=ids, prior_scale=prior_scale, gt=gt, white_noise=white_noise, prev=self._prev_slots,
                           init_action=INIT_ACTION)
         if _phase is not None:
             self.episode[self._reset_ids_host[_phase]] += 1
@@ -1120,4 +1128,4 @@ class VecIPPEnv:
 
     def metrics(self, env_ids=None):
         self.wait()
-        return self.engine.metrics(env_ids=env_ids)
+        return self.engine.metrics(env_ids=env_ids, n=None if env_ids is not None else self.num_envs)  # (the envs, not the spare slots)

@@ -4,6 +4,10 @@ configuration of tests/test_hip_per.py with a small network, and what the iterat
 time of ipp_selfplay_commit_iter + ipp_selfplay_iter_totals + the pinned copy against ipp_selfplay_commit alone, on the same SelfPlay.
 
     python tools/learn_bench.py [--envs 8] [--iterations 2] [--episodes 2] [--sims 24] [--blocks 1] [--steps 12] [--out FILE]
+                                [--planes {dense,compact}]
+
+--planes selects the ring (dense planes per row, or the compact rows of csrc/k_replay_compact.h); "ring" in the output records its
+device bytes, the phase that fills it, the archive launch and one minibatch draw (medians of 3 after a warm-up).
 
 Prints one JSON line (and appends it to --out).  There is no speed bar: the numbers are a record.
 """
@@ -49,6 +53,32 @@ def commit_cost(sp, steps):
     return out
 
 
+def ring_cost(sp, batch, reps=3):
+    """The ring in its mode (dense planes or compact rows), medians of `reps` after a warm-up (ms, CUDA events): the phase of a step that
+    fills the ring, the archive launch between step and commit (compact only), one minibatch draw of `batch` rows; its device bytes."""
+    import numpy as np
+    import torch
+
+    r = sp.replay
+    sp.reset()
+    sp.run(1)
+    sp.timing = {}
+    sp.run(reps)
+    torch.cuda.synchronize()
+    ev, sp.timing = sp.timing, None
+    med = lambda a, b: float(np.median([s.elapsed_time(e) for s, e in zip(ev[a], ev[b])]))  # noqa: E731
+    out = dict(mode="compact" if r.compact is not None else "dense", ring_bytes=r.nbytes(), fill_ms=round(med("planes", "search"), 4),
+               archive_ms=round(med("archive", "commit"), 4) if "archive" in ev else None)
+    r.sample(batch, check_empty=False)
+    r.timing = []
+    for _ in range(reps):
+        r.sample(batch, check_empty=False)
+    torch.cuda.synchronize()
+    out.update(minibatch_rows=batch, minibatch_draw_ms=round(float(np.median([a.elapsed_time(b) for a, b in r.timing])), 4))
+    r.timing = None
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=8)
@@ -58,6 +88,7 @@ def main():
     ap.add_argument("--blocks", type=int, default=1)
     ap.add_argument("--steps", type=int, default=12)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--planes", choices=["dense", "compact"], default="dense", help="the ring: dense planes or compact rows")
     a = ap.parse_args()
     import torch
 
@@ -83,13 +114,15 @@ def main():
     slots = a.iterations * a.episodes * (md["max_episode_steps"] + 1) + 1  # every step of every iteration keeps its slot
     with tempfile.TemporaryDirectory() as tmp:
         t0 = time.perf_counter()
-        lr = Learner(cfg, a.envs, hp, md, module, tmp, episodes_per_env=a.episodes, capacity=a.envs * slots, sims_in_flight=2)
+        lr = Learner(cfg, a.envs, hp, md, module, tmp, episodes_per_env=a.episodes, capacity=a.envs * slots, sims_in_flight=2,
+                     planes=True if a.planes == "dense" else "compact")
         build = time.perf_counter() - t0
         recs = lr.learn()
         sp = lr.selfplay
         cost = commit_cost(sp, a.steps)
-        out = dict(envs=a.envs, sims=a.sims, blocks=a.blocks, episodes_per_env=a.episodes, ring_rows=a.envs * slots,
-                   ring_plane_gib=round(a.envs * slots * 6 * cfg.n_cells ** 2 * 4 / 2 ** 30, 2), build_s=round(build, 2),
+        ring = ring_cost(sp, int(hp["batch_size"]))
+        out = dict(ring=ring, envs=a.envs, sims=a.sims, blocks=a.blocks, episodes_per_env=a.episodes, ring_rows=a.envs * slots,
+                   ring_plane_gib=round(a.envs * slots * 6 * cfg.n_cells ** 2 * 4 / 2 ** 30, 2) if a.planes == "dense" else 0.0, build_s=round(build, 2),
                    iterations=[dict(iteration=r["iteration"], steps=r["totals"]["steps"], examples=r["totals"]["examples"],
                                     window_length=r["window_length"], evicted=r["evicted"],
                                     selfplay_s=round(r["seconds"]["selfplay"], 3), train_s=round(r["seconds"]["train"], 3),

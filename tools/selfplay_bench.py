@@ -6,11 +6,13 @@ and a prioritised-replay leg on the big ring: the PER minibatch (ipp_replay_mass
 against the uniform minibatch (the committed prefix count + ipp_replay_gather) at the same n, alternating.
 
     python tools/selfplay_bench.py [--envs 4096] [--dim 50] [--sims 100] [--steps 8] [--warmup 2] [--planes-envs 8]
-                                   [--per-batch 1024] [--per-reps 20]
+                                   [--per-batch 1024] [--per-reps 20] [--planes {dense,compact}]
 
 The 4096-env run keeps no planes (a 50x50 plane is 25 MB per channel): its planes phase is reported as not measured; the planes phase
 and the gather kernel (CUDA events around the ipp_replay_gather launch alone, one minibatch of --batch rows with one augmented copy) are
-timed on a second, small batch (--planes-envs) with planes in its ring.  Prints one JSON line.
+timed on a second, small batch (--planes-envs) with planes in its ring.  --planes compact gives that batch the compact ring
+(csrc/k_replay_compact.h); "ring" in the output records the ring's device bytes, the phase that fills it, the archive launch and one
+minibatch draw in the chosen mode (medians of 3 after a warm-up).  Prints one JSON line.
 """
 import argparse
 import json
@@ -43,7 +45,7 @@ def timed(sp, steps):
     wall = time.perf_counter() - t0
     ev = sp.timing
     sp.timing = None
-    order = ["planes", "search", "record", "step", "commit", "end"]
+    order = ["planes", "search", "record", "step"] + (["archive"] if "archive" in ev else []) + ["commit", "end"]
     split = {}
     for a, b in zip(order[:-1], order[1:]):
         split[a] = sum(s.elapsed_time(e) for s, e in zip(ev[a], ev[b])) / steps
@@ -92,6 +94,35 @@ def per_leg(sp, n, reps):
             "per_minibatch_and_update_ms": med(per_total), "per_mass_and_draw_ms": med(per_draw), "per_gather_rows_ms": med(per_gather)}
 
 
+def ring_leg(small, batch, reps=3):
+    """What the ring costs in its mode (dense planes or compact rows), medians of `reps` after a warm-up (ms, CUDA events): the phase of
+    a step that fills the ring (ipp_feature_planes into the row, or ipp_replay_record_compact), the archive launch between step and
+    commit (compact only) and one minibatch draw of `batch` rows with one augmented copy (the gather; compact: + the planes of the
+    drawn rows).  And the ring's device bytes."""
+    import numpy as np
+    import torch
+
+    r = small.replay
+    small.run(1)
+    small.timing = {}
+    small.run(reps)
+    torch.cuda.synchronize()
+    ev, small.timing = small.timing, None
+    med = lambda a, b: float(np.median([s.elapsed_time(e) for s, e in zip(ev[a], ev[b])]))  # noqa: E731
+    out = {"mode": "compact" if r.compact is not None else "dense", "envs": small.num_envs, "ring_rows": r.capacity,
+           "ring_bytes": r.nbytes(), "fill_ms": med("planes", "search"),
+           "archive_ms": med("archive", "commit") if "archive" in ev else None}
+    r.sample(batch, num_augmented_samples=1, check_empty=False)
+    r.timing = []
+    for _ in range(reps):
+        r.sample(batch, num_augmented_samples=1, check_empty=False)
+    torch.cuda.synchronize()
+    out["minibatch_rows"] = batch
+    out["minibatch_draw_ms"] = float(np.median([a.elapsed_time(b) for a, b in r.timing]))
+    r.timing = None
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=4096)
@@ -104,6 +135,7 @@ def main():
     ap.add_argument("--batch", type=int, default=96)
     ap.add_argument("--per-batch", type=int, default=1024)
     ap.add_argument("--per-reps", type=int, default=20)
+    ap.add_argument("--planes", choices=["dense", "compact"], default="dense", help="the small batch's ring: dense planes or compact rows")
     a = ap.parse_args()
     import torch
 
@@ -123,7 +155,7 @@ def main():
     # the planes phase with planes in the ring (small batch, history 3, cost plane: 16 channels) and 3-step episodes, so that rows are
     # committed and one minibatch with one augmented copy is gathered (ipp_replay_gather)
     hp3, md3 = params(a.sims, 3)
-    small = SelfPlay(cfg, a.planes_envs, hp3, md3, planes=True, seed=1)
+    small = SelfPlay(cfg, a.planes_envs, hp3, md3, planes=True if a.planes == "dense" else "compact", seed=1)
     small.run(1)
     _, split_small = timed(small, 3)
     small.replay.timing = []
@@ -132,12 +164,13 @@ def main():
     gather_ms = small.replay.timing[0][0].elapsed_time(small.replay.timing[0][1])  # (the ipp_replay_gather kernel alone)
     small.replay.timing = None
     gathered_rows = int((batch[5] >= 0).sum().item())
+    ring = ring_leg(small, a.batch)
     small.close()
     split["planes"] = "not measured: the 4096-env batch keeps no planes (planes=False); see planes_ms_small_batch"
     out = {"envs": a.envs, "grid": a.dim, "sims": a.sims, "steps": a.steps, "samples_per_s": a.envs * a.steps / wall,
            "step_ms": 1e3 * wall / a.steps, "split_ms": split, "episodes_ended_last_step": ended,
            "roots_with_policy_last_step": with_policy, "gather_kernel_ms_small_batch": gather_ms, "gathered_rows": gathered_rows,
-           "prioritised_replay": per,
+           "prioritised_replay": per, "ring": ring,
            "planes_ms_small_batch": {"envs": a.planes_envs, "planes": split_small["planes"], "record": split_small["record"]}}
     print(json.dumps(out))
 

@@ -72,6 +72,9 @@ typedef struct ipp_field_record {
                                 /* restarts and refill[position] names it for ipp_generate_grf_refill                           */
 #define IPP_BUDGET_STREAM (3ull << 40) /* Philox subsequence base of the shuffled start budgets: episode j of global env g draws  */
                                        /* its budget from subsequence IPP_BUDGET_STREAM + j, counter g                          */
+#define IPP_PRIOR_STREAM (11ull << 40) /* Philox subsequence base of the per-episode priors (ipp_set_budget_prior): episode j of global */
+                                       /* env g draws sigma^2 from counter 2 g and l from counter 2 g + 1 of subsequence               */
+                                       /* IPP_PRIOR_STREAM + j (10ull << 40 is the baseline planners' IPP_BASELINE_STREAM)             */
 #define IPP_CMA_STREAM    (9ull << 40) /* Philox subsequence base of the CMA-ES planner's normals: generation g of a policy's r-th  */
                                        /* replan draws row (global env id) of subsequence IPP_CMA_STREAM + r * max_iter + g; the    */
                                        /* bases 1..8 << 40 are the ground-truth, noise, budget, self-play and replay streams          */
@@ -303,11 +306,28 @@ int ipp_set_reset_prior(void* engine, const double* prior);
  *   initial_budget, shuffle_budget  start budget of an episode: initial_budget, or floor(10 + u (initial_budget - 10)) with u the
  *                                   Philox uniform of counter (env + row_offset), subsequence IPP_BUDGET_STREAM + episode, key seed
  *   max_steps                       max_episode_steps
- * A reset on done is ipp_step_autoreset's flip to the alternate ground-truth plane (reset_gt == NULL): mean 0.5, the config's prior,
- * rank 0, prev_action[env] <- init_action; ipp_generate_grf_refill stages the next field behind every such step.
+ * A reset on done is ipp_step_autoreset's flip to the alternate ground-truth plane (reset_gt == NULL): mean 0.5, the config's prior
+ * (or the new episode's own: ipp_set_budget_prior), rank 0, prev_action[env] <- init_action; ipp_generate_grf_refill stages the next field behind every such step.
  */
 int ipp_set_budget(void* engine, double* budget, int32_t* depth, int64_t* episode, uint8_t* done, int32_t* refill,
                    double initial_budget, int32_t max_steps, int32_t shuffle_budget, uint64_t seed, int64_t row_offset);
+
+/*
+ * Per-episode priors of the budget ledger: shuffle_prior_cov of the self-play loop.  Replaces the draw of
+ * mapping/mappings.py:238-240 (signal_variance = np.random.uniform(0.8, 1.2) * signal_variance, then the same for length_scale), made
+ * once per episode where planning/mcts_zero/episode_generators.py:53 builds the episode's Mapping (config/example.yaml:106).
+ * Call it after ipp_set_budget: it uses that ledger's seed and row_offset (ipp_set_budget installs a ledger WITHOUT per-episode priors).
+ *   shuffle_prior = 1   every reset on done of an IPP_BUDGET | IPP_RESET_ON_DONE step installs the prior of the episode it starts:
+ *                       value = lo + (hi - lo) u, lo = 0.8 nominal, hi = 1.2 nominal (NumPy's form of uniform(lo, hi)), every product
+ *                       and sum rounded to fp64 on its own, u = (word 0 + 0.5) 2^-32 of Philox4x32-10 at counter 2 g (sigma^2) and
+ *                       2 g + 1 (l), g = env + row_offset, subsequence IPP_PRIOR_STREAM + episode, key seed.  The caller installs
+ *                       the same pair for the episodes it starts itself (ipp_reset_episode's prior_scale).
+ *   shuffle_prior = 0   (the default) the config's prior, as without the call.
+ * Refused, the ledger untouched: no ledger installed; not a patch-layout engine; a windowed engine created with
+ * ipp_config.fixed_prior = 1, whose column window does not cover a length scale of 1.2 x nominal (the reset would poison the env).
+ * ipp_selfplay_archive then archives the prior of the episode that ENDED (drawn again from its index), not the slot's current pair.
+ */
+int ipp_set_budget_prior(void* engine, int32_t shuffle_prior);
 
 /*
  * Reward of n candidate actions from the CURRENT state of ONE env slot; nothing is written.  The call of
@@ -676,6 +696,10 @@ int ipp_read_gt(void* engine, int32_t env_id, float* out /*[N]*/, void* stream);
 int ipp_read_cov_dense(void* engine, int32_t env_id, float* out /*[N][N]*/, void* stream);
 int ipp_read_rank(void* engine, int32_t env_id, int32_t* rank /*[host] out*/, void* stream); /* synchronises */
 int ipp_read_ranks(void* engine, int32_t* out /*[dev] int32[capacity]*/, void* stream);      /* all slots, async */
+/* The prior (sigma^2, l) of n slots -- the episode's Mapping.signal_variance / length_scale (mapping/mappings.py:238-240) -- as
+ * double[n][2]; env_ids [dev] int32[n], or NULL: slots 0 .. n - 1.  A slot id outside the engine reads NaN.  out: [dev], 16-byte
+ * aligned.  Async. */
+int ipp_read_prior(void* engine, const int32_t* env_ids, int32_t n, double* out /*[dev][n][2]*/, void* stream);
 
 /* Inject state (reference callers assign grid_map.mean / grid_map.cov_matrix directly:
  * planning/mcts_mission.py:395,413; adaptive_info["mean"], planning/common/optimization.py:22-25).

@@ -16,6 +16,7 @@ IPP_PRIOR_MATERN32, IPP_PRIOR_MATERN12, IPP_PRIOR_MATERN52, IPP_PRIOR_RBF = 0, 1
 IPP_COV_ONLY, IPP_PREDICT_ONLY, IPP_ADAPTIVE, IPP_USE_FLIGHT_TIME, IPP_GIVEN_OBSERVATION, IPP_UPDATE_PREV = 1, 2, 4, 8, 16, 32
 IPP_BUDGET, IPP_RESET_ON_DONE = 64, 128
 IPP_BUDGET_STREAM = 3 << 40
+IPP_PRIOR_STREAM = 11 << 40  # Philox subsequence base of the per-episode priors (ipp_set_budget_prior, vec_env.start_prior)
 IPP_CMA_STREAM = 9 << 40  # Philox subsequence base of the CMA-ES planner's normals (planning/vec_cmaes.py)
 IPP_CMA_MAX_DIM, IPP_CMA_MAX_LAMBDA = 48, 64
 # Philox subsequence bases of the self-play draws (ipp_selfplay_record / _commit, ipp_replay_gather)
@@ -243,6 +244,7 @@ PROTOTYPES = {
     "ipp_generate_field_refill": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, C.c_int64, C.c_uint64, C.c_uint64, _P]),
     "ipp_fill_fields": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
     "ipp_set_budget": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_double, C.c_int32, C.c_int32, C.c_uint64, C.c_int64]),
+    "ipp_set_budget_prior": (C.c_int, [_P, C.c_int32]),
     "ipp_step": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, C.c_uint32, _P, _P, _P]),
     "ipp_step_autoreset": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P]),
     "ipp_step_parts": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, C.c_int32, _P, _P]),
@@ -258,6 +260,7 @@ PROTOTYPES = {
     "ipp_read_cov_dense": (C.c_int, [_P, C.c_int32, _P, _P]),
     "ipp_read_rank": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), _P]),
     "ipp_read_ranks": (C.c_int, [_P, _P, _P]),
+    "ipp_read_prior": (C.c_int, [_P, _P, C.c_int32, _P, _P]),
     "ipp_write_mean": (C.c_int, [_P, C.c_int32, _P, _P]),
     "ipp_write_gt": (C.c_int, [_P, C.c_int32, _P, _P]),
     "ipp_write_cov_dense": (C.c_int, [_P, C.c_int32, _P, _P]),

@@ -43,6 +43,10 @@ __device__ __forceinline__ const float* uni_ptr(const float* p) {  // wave-unifo
 __device__ __forceinline__ double uni(double x) {
     return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(x)), __builtin_amdgcn_readfirstlane(__double2loint(x)));
 }
+__device__ __forceinline__ long long uni_ll(long long x) {
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)x), hi = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)x >> 32));
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
 __device__ __forceinline__ ItemHdr uniform_hdr(const ItemHdr& h) {
     ItemHdr o;
     o.env = uni(h.env); o.dst = uni(h.dst); o.rank = uni(h.rank); o.status = uni(h.status);
@@ -190,10 +194,13 @@ struct Ledger {
     unsigned char* done; // [n] per item of the last step
     int* refill;        // [n] per dispatch position of the last IPP_RESET_ON_DONE step: the env that reset there, else -1
     double b0, res;     // initial_budget, grid resolution (the loop's threshold)
-    int max_steps, shuffle;
+    int max_steps, shuffle;  // shuffle: bit set, kLedgerShuffleBudget | kLedgerShufflePrior
     uint64_t seed;
     long long row_offset;
 };
+
+constexpr int kLedgerShuffleBudget = 1;  // start budgets floor(U(10, b0)) (ipp_set_budget, budget_start)
+constexpr int kLedgerShufflePrior = 2;   // a reset on done installs the drawn prior of the episode it starts (ipp_set_budget_prior, prior_start)
 
 // Episode reset folded into a step launch (ipp_step_autoreset): item i resets its env after its step when
 // src[i] >= 0, taking ground truth gt[src[i]] ([N] floats).  Mission.init_action by value.
@@ -251,7 +258,7 @@ __device__ __forceinline__ void philox_normal4(uint64_t q, uint64_t subseq, uint
 // int(U(10, initial_budget))): floor(10 + u (b0 - 10)), u the Philox4x32-10 uniform of counter (env + row_offset),
 // subsequence IPP_BUDGET_STREAM + episode, key seed -- keyed on the global env id like the ground truths.
 __device__ __forceinline__ double budget_start(const Ledger& L, int env, long long episode) {
-    if (!L.shuffle) return L.b0;
+    if (!(L.shuffle & kLedgerShuffleBudget)) return L.b0;
     const uint64_t q = (uint64_t)((long long)env + L.row_offset), sub = (uint64_t)IPP_BUDGET_STREAM + (uint64_t)episode;
     uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32), (uint32_t)sub, (uint32_t)(sub >> 32)};
     uint32_t k[2] = {(uint32_t)L.seed, (uint32_t)(L.seed >> 32)};
@@ -260,17 +267,45 @@ __device__ __forceinline__ double budget_start(const Ledger& L, int env, long lo
     return floor(__dadd_rn(10.0, __dmul_rn(u, L.b0 - 10.0)));  // (rounded product, then the sum: no contraction, the host's NumPy value)
 }
 
+// Prior (sigma^2, l) of episode `episode` of env `env` under shuffle_prior_cov (mapping/mappings.py:238-240: np.random.uniform(0.8, 1.2)
+// times the nominal value, sigma^2 drawn before l): lo + (hi - lo) u with lo = 0.8 nominal, hi = 1.2 nominal -- NumPy's own form of
+// uniform(lo, hi) -- and u the Philox4x32-10 uniform (word 0) of counter 2 g (sigma^2) / 2 g + 1 (l), g = env + row_offset the global
+// env id, subsequence IPP_PRIOR_STREAM + episode, key seed.  Every product and sum rounded on its own (no contraction): vec_env.start_prior
+// is the same number bit for bit.  Uniform arguments give a uniform result (the resetting wave needs sigma^2 in every lane before its fill).
+__device__ __forceinline__ double prior_uniform(uint64_t q, uint64_t sub, uint64_t seed) {
+    uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32), (uint32_t)sub, (uint32_t)(sub >> 32)};
+    uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+    for (int r = 0; r < 10; ++r) philox_round(c, k);
+    return ((double)c[0] + 0.5) * (1.0 / 4294967296.0);  // (exact: a 33-bit integer times a power of two)
+}
+__device__ __forceinline__ double prior_draw(double nominal, double u) {
+    // contraction off for these statements: the header's __dmul_rn / __dadd_rn are a plain product and sum that the compiler fuses
+    // with their neighbours after inlining (an FMA skips the product's rounding: the last bit of one draw in four differed from NumPy's)
+#pragma clang fp contract(off)
+    const double lo = 0.8 * nominal, hi = 1.2 * nominal;
+    const double span = hi - lo;
+    const double step = span * u;
+    return lo + step;
+}
+__device__ __forceinline__ void prior_start(double sv0, double ls0, uint64_t seed, long long row_offset, int env, long long episode,
+                                            double& sv, double& ls) {
+    const uint64_t g = (uint64_t)((long long)env + row_offset), sub = (uint64_t)IPP_PRIOR_STREAM + (uint64_t)episode;
+    sv = prior_draw(sv0, prior_uniform(2 * g, sub, seed));
+    ls = prior_draw(ls0, prior_uniform(2 * g + 1, sub, seed));
+}
+
 // One wave resets env `env` (mapping/mappings.py:235-240,259-261: mean 0.5, P = prior; factor state: rank 0) and
 // installs ground truth field k.  The caller guarantees that every earlier store / atomic to the env's planes
 // has completed.
 // INVARIANT the compact replay ring rests on (k_replay_compact.h, k_rc_archive): a reset rewrites mean, diag, the ground-truth
 // plane or gt_slot, rank, prior and prev, and NOTHING of the column storage (cov, colspan, colrect).  The step that ended the episode
 // appended its columns behind the rank it found, so after a step with a reset the columns [0, pre-step rank) of the ended episode
-// are still intact and can be archived behind the launch (tests/test_hip_replay_compact.py pins it bit for bit).
-__device__ __forceinline__ void wave_reset_env(const View& v, const AutoReset& ar, int env, int k, int lane) {
-    // (prior of the new episode like k_reset_small: shuffle_prior_cov scales, mappings.py:238-240; a length scale the column
-    // window was not sized for poisons the env instead of losing accuracy silently)
-    double sv_d = ar.prior ? ar.prior[2 * k + 0] : v.sv0, ls_d = ar.prior ? ar.prior[2 * k + 1] : v.ls0;
+// are still intact and can be archived behind the launch (tests/test_hip_replay_compact.py pins it bit for bit).  The prior pair IS
+// rewritten: with per-episode priors (ipp_set_budget_prior) the slot holds the NEXT episode's pair behind the launch, and the archive
+// recomputes the ended episode's from its index (prior_start) instead of copying the slot's.
+// (sv_d, ls_d): the new episode's prior.
+__device__ __forceinline__ void wave_reset_env_prior(const View& v, const AutoReset& ar, int env, int k, int lane, double sv_d, double ls_d) {
+    // (a length scale the column window was not sized for poisons the env instead of losing accuracy silently)
     if (v.ls_max > 0.0 && ls_d > v.ls_max * (1.0 + 1e-12)) sv_d = ls_d = NAN;
     float* mean = v.mean + (size_t)env * v.Npad;
     float* diag = v.diag + (size_t)env * v.Npad;
@@ -347,6 +382,11 @@ __device__ __forceinline__ void wave_reset_env(const View& v, const AutoReset& a
         v.prior[2 * env + 1] = ls_d;
     }
     if (ar.prev && lane < 3) ar.prev[3 * env + lane] = ar.init[lane];
+}
+__device__ __forceinline__ void wave_reset_env(const View& v, const AutoReset& ar, int env, int k, int lane) {
+    // (prior of the new episode like k_reset_small: shuffle_prior_cov scales, mappings.py:238-240)
+    const double sv_d = ar.prior ? ar.prior[2 * k + 0] : v.sv0, ls_d = ar.prior ? ar.prior[2 * k + 1] : v.ls0;
+    wave_reset_env_prior(v, ar, env, k, lane, sv_d, ls_d);
 }
 
 __device__ __forceinline__ double wave_sum(double x) {

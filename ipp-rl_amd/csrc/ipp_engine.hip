@@ -1178,9 +1178,36 @@ int ipp_set_budget(void* engine, double* budget, int32_t* depth, int64_t* episod
     if (max_steps < 1) return fail(-1, "ipp_set_budget: max_steps < 1");
     Ledger L = {};
     L.budget = budget; L.depth = depth; L.episode = reinterpret_cast<long long*>(episode); L.done = done; L.refill = refill;
-    L.b0 = initial_budget; L.res = e->v.res; L.max_steps = max_steps; L.shuffle = shuffle_budget ? 1 : 0; L.seed = seed;
+    L.b0 = initial_budget; L.res = e->v.res; L.max_steps = max_steps; L.shuffle = shuffle_budget ? kLedgerShuffleBudget : 0; L.seed = seed;
     L.row_offset = (long long)row_offset;
     e->led = L;
+    return 0;
+}
+
+int ipp_set_budget_prior(void* engine, int32_t shuffle_prior) {
+    Engine* e = as_engine(engine);
+    if (!e) return fail(-1, "null engine");
+    if (!e->led.budget) return fail(-1, "ipp_set_budget_prior: no ledger installed (ipp_set_budget)");
+    if (!e->patch || e->v.mode != IPP_FACTOR) return fail(-1, "ipp_set_budget_prior: patch-layout factor engines only (ipp_info.patch_layout == 1)");
+    if (shuffle_prior && e->v.ls_max > 0.0 && e->cfg.fixed_prior)
+        return fail(-1, "ipp_set_budget_prior: the column window (%d rows) was sized for the nominal length scale (ipp_config.fixed_prior = 1): "
+                        "a drawn length scale of up to 1.2 x %g m would poison envs; create the engine with fixed_prior = 0",
+                    e->v.window_rows, e->cfg.length_scale);
+    if (shuffle_prior) e->led.shuffle |= kLedgerShufflePrior;
+    else e->led.shuffle &= ~kLedgerShufflePrior;
+    return 0;
+}
+
+int ipp_read_prior(void* engine, const int32_t* env_ids, int32_t n, double* out, void* stream) {
+    Engine* e = as_engine(engine);
+    if (!e || !out) return fail(-1, "null argument");
+    if (n < 0 || (!env_ids && n > e->v.cap)) return fail(-1, "ipp_read_prior: n = %d outside [0, capacity = %d]", n, e->v.cap);
+    if (reinterpret_cast<uintptr_t>(out) & 15u) return fail(-1, "ipp_read_prior: out must be 16-byte aligned");
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(e->device));
+    hipLaunchKernelGGL(k_read_prior, dim3((n + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), e->v, env_ids, n,
+                       reinterpret_cast<double2*>(out));
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -1481,7 +1508,9 @@ int ipp::factor_slots(void* engine, FactorSlots* out) {
     if (!e) return fail(-1, "null engine");
     const View& v = e->v;
     *out = FactorSlots{e->device, v.cap, v.rank_cap, v.N, v.Npad, v.pstride, e->patch && v.mode == IPP_FACTOR, v.cov_slot,
-                       v.cov, v.colspan, v.colrect, v.rank, v.prior, v.mean};
+                       v.cov, v.colspan, v.colrect, v.rank, v.prior, v.mean,
+                       (e->led.budget && (e->led.shuffle & kLedgerShufflePrior)) ? 1 : 0, v.sv0, v.ls0, e->led.seed, e->led.row_offset,
+                       e->led.depth, e->led.episode};
     return 0;
 }
 

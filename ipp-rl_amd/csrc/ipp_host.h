@@ -26,6 +26,13 @@ struct FactorSlots {
     bool patch;
     uint64_t cov_slot;  // floats per slot
     float* cov; int* colspan; int* colrect; int* rank; double* prior; const float* mean;
+    // per-episode priors of the budget ledger (ipp_set_budget_prior; prior_shuffle == 0: off, the rest unused): what prior_start needs
+    // to name the prior of an episode again, and the ledger's depth / episode arrays [capacity]
+    int prior_shuffle;
+    double sv0, ls0;
+    uint64_t prior_seed;
+    long long prior_row_offset;
+    const int* led_depth; const long long* led_episode;
 };
 int factor_slots(void* engine, FactorSlots* out);  // (null engine: "null engine")
 

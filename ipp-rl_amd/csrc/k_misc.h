@@ -66,6 +66,15 @@ __global__ void k_reset_flagged(View v, const int* __restrict__ env_ids, int n_i
     if (ar.gt) gt_plane(v, env)[cell] = valid ? ar.gt[(size_t)k * v.N + cell] : 0.f;
 }
 
+// ipp_read_prior: the (sigma^2, l) pairs of n slots as one 16-byte vector store each; a slot outside the engine reads NaN
+__global__ __launch_bounds__(256) void k_read_prior(View v, const int* __restrict__ env_ids, int n, double2* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int env = env_ids ? env_ids[i] : i;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    out[i] = (env >= 0 && env < v.cap) ? make_double2(v.prior[2 * env + 0], v.prior[2 * env + 1]) : make_double2(nan, nan);
+}
+
 // ipp_read_gt / ipp_write_gt: the env's CURRENT ground-truth plane (the slot lives on the device)
 __global__ void k_copy_gt(View v, int env, float* __restrict__ out, const float* __restrict__ in) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

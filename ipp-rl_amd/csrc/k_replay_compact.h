@@ -5,7 +5,7 @@
 //   k_rc_record    one workgroup per env, before the search: the env's history entries into its ring row (entry 0's rank made explicit,
 //                  every valid entry's slot replaced by the archive slot the running episode will get), its current mean, the episode tag
 //   k_rc_archive   after the budget step, before the commit: workgroups of envs whose episode did not end exit at once; the others copy
-//                  the columns [0, r_last) of the env slot, their spans and rectangles and the prior pair into the archive slot, rank
+//                  the columns [0, r_last) of the env slot, their spans and rectangles and the ENDED episode's prior pair into the archive slot, rank
 //                  r_last + 1 (every sample of the episode is a strict prefix: k_feature_planes.h, plane_diag).  What makes the copy
 //                  valid AFTER the step's reset: wave_reset_env (ipp_common.h) leaves the column storage alone.
 //   k_rc_evict     the archive slot of episode p held episode p - E: the env's ring rows still tagged p - E lose their flag (counted),
@@ -74,8 +74,14 @@ __global__ __launch_bounds__(256) void k_rc_archive(ipp_selfplay sp, ipp_replay_
             fs.colrect[(size_t)dst * fs.rank_cap + k] = fs.colrect[(size_t)e * fs.rank_cap + k];
         }
         if (threadIdx.x == 0) {
-            fs.prior[2 * dst + 0] = fs.prior[2 * e + 0];
-            fs.prior[2 * dst + 1] = fs.prior[2 * e + 1];
+            // the prior of the episode that ENDED.  With the config's prior in every episode that is the slot's pair.  With per-episode
+            // priors (ipp_set_budget_prior) the step's reset has already installed the next episode's pair in the slot (depth 0, the episode
+            // counter advanced: ledger_close), and the ended episode's is drawn again from its index -- the same number, prior_start
+            double sv = fs.prior[2 * e + 0], ls = fs.prior[2 * e + 1];
+            if (fs.prior_shuffle && fs.led_depth[e] == 0)
+                prior_start(fs.sv0, fs.ls0, fs.prior_seed, fs.prior_row_offset, e, fs.led_episode[e] - 1, sv, ls);
+            fs.prior[2 * dst + 0] = sv;
+            fs.prior[2 * dst + 1] = ls;
             fs.rank[dst] = r + 1;  // never stepped: the field only bounds the prefixes, and keeps every sample off the slot's stored diag
         }
     }

@@ -157,7 +157,18 @@ __device__ __forceinline__ void ledger_close(const View& v, const AutoReset& ar,
     const Ledger& L = ar.led;
     const bool done = ledger_done(L, bud, dep, cost);
     const bool rs = done && (flags & IPP_RESET_ON_DONE);
-    if (rs) wave_reset_env(v, ar, env, 0, lane);  // (reset_gt == NULL, no reset prior: k is not read)
+    if (rs) {
+        if (L.shuffle & kLedgerShufflePrior) {
+            // the prior of the episode this reset starts (ipp_set_budget_prior): the episode counter is a uniform load and the draw
+            // uniform arithmetic, so every lane holds sigma^2 when the fill of the variance plane starts -- no second pass, no broadcast
+            const long long ep_next = uni_ll(L.episode[env]) + 1;
+            double sv_n, ls_n;
+            prior_start(v.sv0, v.ls0, L.seed, L.row_offset, env, ep_next, sv_n, ls_n);
+            wave_reset_env_prior(v, ar, env, 0, lane, sv_n, ls_n);
+        } else {
+            wave_reset_env(v, ar, env, 0, lane);  // (reset_gt == NULL, no reset prior: k is not read)
+        }
+    }
     if (lane == 0) {
         L.done[item] = done ? 1 : 0;
         if (rs) {

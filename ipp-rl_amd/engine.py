@@ -799,6 +799,12 @@ class IPPEngine:
                                             self._ptr(refill), float(initial_budget), int(max_steps), int(bool(shuffle_budget)),
                                             int(seed) & (2 ** 64 - 1), int(row_offset)))
 
+    def set_budget_prior(self, shuffle_prior: bool):
+        """ipp_set_budget_prior, after set_budget: True = every reset on done of a budget step installs the drawn prior of the episode
+        it starts (vec_env.start_prior: the ledger's seed and row_offset); False = the config's prior (the default).  Refused (IppError)
+        without a ledger, on an engine that is not patch-layout, and on a windowed engine built with fixed_prior=True."""
+        _ffi.check(self._lib.ipp_set_budget_prior(self._h, int(bool(shuffle_prior))))
+
     def generate_grf_refill(self, n: int, refill, episode, seed: int, subsequence: int, row_offset: int = 0, stream=None) -> bool:
         """ipp_generate_grf_refill: field i into the alternate plane of env refill[i] (negative: skipped), noise subsequence
         subsequence + episode[env] + 1 (refill / episode: device tensors, e.g. views into the installed ledger).  False: this grid
@@ -897,6 +903,16 @@ class IPPEngine:
         if out is None:
             out = torch.empty(self.capacity, dtype=torch.int32, device=self.device)
         _ffi.check(self._lib.ipp_read_ranks(self._h, self._ptr(out), self.stream))
+        return out
+
+    def priors(self, env_ids=None):
+        """Prior (sigma^2, l) of the given slots (None: every slot) as a device float64 tensor [n, 2] (ipp_read_prior; no host sync)."""
+        torch = _torch()
+        ids = self._dev(env_ids, torch.int32)
+        n = self.capacity if ids is None else int(ids.numel())
+        out = torch.empty((n, 2), dtype=torch.float64, device=self.device)
+        _ffi.check(self._lib.ipp_read_prior(self._h, self._ptr(ids), n, self._ptr(out), self.stream))
+        self._keep = (ids,)
         return out
 
     def write_mean(self, env, mean):

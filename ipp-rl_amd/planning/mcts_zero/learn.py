@@ -93,8 +93,10 @@ class Learner:
         arena_envs: envs of the gate's arena (default gcd(num_arena_games, num_envs)).  net_max_batch: leaves one forward of a device
         network takes (default max(num_envs, arena_envs) x sims_in_flight).  selfplay_kwargs go to SelfPlay (capacity: the ring has to
         hold the rows of a whole off-policy window, see INTEGRATION.md "Learn loop"; planes="compact" and archive_episodes: the compact
-        ring, whose rows are a few KB, so that such a window fits beside thousands of envs); sims_in_flight, tie_break and groups go to the
-        arena too."""
+        ring, whose rows are a few KB, so that such a window fits beside thousands of envs; episode_priors="device": a true
+        hyper_params["shuffle_prior_cov"] -- config/example.yaml's setting -- gives every self-play episode its own prior, drawn on the
+        device, vec_env.start_prior; the arena stays on the config's prior, as the reference's does, and learn_state.pt needs nothing new:
+        the priors are a function of seed, global env id and episode index); sims_in_flight, tie_break and groups go to the arena too."""
         self.episodes_per_env, self.arena_envs = check_args(hyper_params, num_envs, episodes_per_env, arena_envs)
         import torch
 

@@ -257,8 +257,12 @@ def window_rows_host(flags, r_iter, lo: int, hi: int) -> np.ndarray:
     return np.nonzero((f == COMMITTED) & (t >= int(lo)) & (t <= int(hi)))[0].astype(np.int64)
 
 
-def check_args(hyper_params: Dict, meta_data: Dict, num_envs: int, capacity: Optional[int]):
-    """What SelfPlay cannot run, refused before anything touches the device.  Returns (slots S, max_episode_steps)."""
+def check_args(hyper_params: Dict, meta_data: Dict, num_envs: int, capacity: Optional[int], episode_priors: Optional[str] = None):
+    """What SelfPlay cannot run, refused before anything touches the device.  Returns (slots S, max_episode_steps).
+    episode_priors: None (a true hyper_params["shuffle_prior_cov"] raises) or "device" (it selects the env's device-drawn per-episode
+    priors, VecIPPEnv(shuffle_prior_cov="device"))."""
+    if episode_priors is not None and episode_priors != "device":
+        raise ValueError(f"episode_priors = {episode_priors!r}: None or 'device'")
     if meta_data.get("initial_budget") is None:
         raise ValueError("self-play runs budget-mode episodes: meta_data['initial_budget'] is needed")
     if not hyper_params.get("reset_mcts_each_step", True):
@@ -266,8 +270,10 @@ def check_args(hyper_params: Dict, meta_data: Dict, num_envs: int, capacity: Opt
     if hyper_params.get("use_per", False):
         raise ValueError("use_per=True is the trainer's switch, not the episode loop's: it is not supported here; draw prioritised "
                          "minibatches with SelfPlay.replay.prioritized(...) (ReplayBuffer.prioritized)")
-    if hyper_params.get("shuffle_prior_cov", False):
-        raise ValueError("shuffle_prior_cov=True (per-episode shuffled priors) is not supported in budget mode")
+    if hyper_params.get("shuffle_prior_cov", False) and episode_priors is None:
+        raise ValueError("shuffle_prior_cov=True (per-episode shuffled priors) needs the opt-in episode_priors='device': the priors are then "
+                         "drawn per episode from the device's Philox streams (vec_env.start_prior) -- the reference's distribution, "
+                         "U(0.8, 1.2) x nominal, but not the values of NumPy's global stream")
     steps = int(meta_data.get("max_episode_steps", hyper_params.get("max_episode_steps", 0)))
     if steps < 1 or steps >= MAX_DEPTH:
         raise ValueError(f"max_episode_steps = {steps} outside [1, 2^20)")
@@ -614,7 +620,7 @@ class SelfPlay:
     def __init__(self, cfg, num_envs: int, hyper_params: Dict, meta_data: Dict, infer: Optional[Callable] = None,
                  capacity: Optional[int] = None, seed: int = 0, env_id_offset: int = 0, random_init_action: bool = True,
                  planes=True, sims_in_flight: int = 4, tie_break: str = "first", groups: int = 2, device: str = "cuda:0",
-                 archive_episodes: Optional[int] = None, **env_kwargs):
+                 archive_episodes: Optional[int] = None, episode_priors: Optional[str] = None, **env_kwargs):
         """cfg: EngineConfig; hyper_params / meta_data: the reference's dictionaries (config/example.yaml: gamma, puct_*, dirichlet_*,
         num_mcts_simulations, temperature_scale / _threshold, input_history_length, use_fov_input, use_action_costs_input, shuffle_budget;
         initial_budget, max_episode_steps, episode_horizon, min / max_altitude, altitude_spacing, uav_specifications, scenario_info).
@@ -625,8 +631,14 @@ class SelfPlay:
         engine slot; the planes are built when a minibatch is drawn (ReplayBuffer).  archive_episodes = E: archive slots per env
         (spare_slots = num_envs E go to the env); None: the ring's step slots S, with which nothing is evicted; a smaller E evicts
         the rows of episode p - E when episode p ends: E >= S / (steps of the shortest episode expected) avoids it.
+        episode_priors: None -- a true hyper_params["shuffle_prior_cov"] raises; "device" -- hyper_params["shuffle_prior_cov"] decides:
+        True gives every episode its own prior (sigma^2, l) ~ U(0.8, 1.2) x nominal (mapping/mappings.py:238-240), drawn on the device
+        by the reset that starts it (VecIPPEnv(shuffle_prior_cov="device"), vec_env.start_prior); False is the config's prior, bit for
+        bit the run without the argument.
         env_kwargs go to VecIPPEnv."""
-        S, steps = check_args(hyper_params, meta_data, num_envs, capacity)
+        S, steps = check_args(hyper_params, meta_data, num_envs, capacity, episode_priors)
+        if episode_priors == "device" and hyper_params.get("shuffle_prior_cov", False):
+            env_kwargs["shuffle_prior_cov"] = "device"
         E = check_replay_mode(planes, archive_episodes, S)
         if E:
             from ...engine import patch_layout_possible

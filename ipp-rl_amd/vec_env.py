@@ -103,6 +103,30 @@ def start_budget(initial_budget: float, shuffle_budget: bool, seed: int, global_
     return np.floor(10.0 + u * (float(initial_budget) - 10.0))
 
 
+PRIOR_LOW, PRIOR_HIGH = 0.8, 1.2  # shuffle_prior_cov: np.random.uniform(0.8, 1.2) x nominal (mapping/mappings.py:238-240)
+
+
+def prior_from_uniform(nominal: float, u):
+    """np.random.uniform(0.8 nominal, 1.2 nominal) as NumPy's legacy generator forms it from its uniform u in [0, 1):
+    low + (high - low) u, every product and sum rounded to fp64 on its own (the device: prior_draw, csrc/ipp_common.h)."""
+    lo, hi = np.float64(PRIOR_LOW) * np.float64(nominal), np.float64(PRIOR_HIGH) * np.float64(nominal)
+    return lo + (hi - lo) * np.asarray(u, dtype=np.float64)
+
+
+def start_prior(cfg: EngineConfig, seed: int, global_env_ids, episode) -> np.ndarray:
+    """Prior (sigma^2, l) of episode `episode` of the given GLOBAL env ids under shuffle_prior_cov="device", float64 [n, 2]: the
+    reference's per-episode draw (mapping/mappings.py:238-240, sigma^2 before l) from the device's Philox streams --
+    u_sigma = philox_uniform(2 g, IPP_PRIOR_STREAM + episode, seed), u_l = philox_uniform(2 g + 1, ...), value =
+    prior_from_uniform(nominal, u).  What the budget step installs on the device when it resets an env (prior_start,
+    csrc/ipp_common.h), bit for bit; a function of (seed, global env id, episode) alone."""
+    gid = np.asarray(global_env_ids, dtype=np.int64).reshape(-1)
+    sub = _ffi.IPP_PRIOR_STREAM + np.broadcast_to(np.asarray(episode, dtype=np.int64), gid.shape)
+    out = np.empty((len(gid), 2), dtype=np.float64)
+    for d, nominal in enumerate((cfg.signal_variance, cfg.length_scale)):
+        out[:, d] = prior_from_uniform(nominal, philox_uniform(2 * gid + d, sub, seed))
+    return out
+
+
 def shard_range(total: int, rank: int, world: int):
     """Contiguous env-id range of `rank`: [rank*total/world, (rank+1)*total/world)."""
     lo = (total * rank) // world
@@ -146,7 +170,10 @@ class VecIPPEnv:
         carries a device-side ledger (self.budget, self.depth, self.episode, self.done) that the step kernel charges with the action
         cost, and an env whose loop condition fails is reset inside the step launch; its next ground truth is generated behind
         the step from the device's refill list (no device->host sync in the loop).  shuffle_budget: start budgets
-        floor(U(10, B0)) per env and episode (start_budget).  node_capacity / max_batch: the engine's tree nodes and largest launch
+        floor(U(10, B0)) per env and episode (start_budget).  shuffle_prior_cov="device" (budget mode only; True stays the scheduled
+        mode's host table and raises here): every episode's prior is (sigma^2, l) ~ U(0.8, 1.2) x nominal (mapping/mappings.py:238-240),
+        drawn by the reset on done from the device's Philox streams (start_prior); the engine's column window gets the 1.2 x
+        head-room (fixed_prior=False).  node_capacity / max_batch: the engine's tree nodes and largest launch
         (IPPEngine), for a search whose roots are the env slots (planning/mcts_zero/selfplay.py); the defaults build no nodes and launches of
         num_envs items.  spare_slots=K: the engine gets num_envs + K slots; [0, num_envs) are the envs, the slots above them are never
         stepped or reset by the env (the compact replay ring archives ended episodes there); K = 0 builds exactly the engine without it."""
@@ -162,6 +189,13 @@ class VecIPPEnv:
         self.seed = int(seed)
         self.env_id_offset = int(env_id_offset)
         self.shuffle_prior_cov = shuffle_prior_cov
+        # "device": budget mode's per-episode priors, drawn on the device by the reset on done (start_prior)
+        self.device_priors = isinstance(shuffle_prior_cov, str) and shuffle_prior_cov == "device"
+        if isinstance(shuffle_prior_cov, str) and not self.device_priors:
+            raise ValueError(f"shuffle_prior_cov = {shuffle_prior_cov!r}: False, True or 'device'")
+        if self.device_priors and budget is None:
+            raise ValueError("shuffle_prior_cov='device' draws an episode's prior in the budget step's reset on done: budget mode only "
+                             "(VecIPPEnv(budget=...)); the scheduled mode takes shuffle_prior_cov=True")
         self.adaptive, self.use_flight_time = adaptive, use_flight_time
         self.budget_mode = budget is not None
         self.check_feature_history(feature_history, budget)
@@ -172,8 +206,10 @@ class VecIPPEnv:
         if self.field_kind == _ffi.IPP_FIELD_HOTSPOT:
             check_hotspot(cfg.y_dim, cfg.x_dim, cfg.cluster_radius)
         if self.budget_mode:
-            if shuffle_prior_cov:
-                raise ValueError("budget mode: per-episode shuffled priors are not supported (shuffle_prior_cov)")
+            if shuffle_prior_cov and not self.device_priors:
+                raise ValueError("budget mode: shuffle_prior_cov=True names the scheduled mode's host table of priors, which a reset inside "
+                                 "the step launch cannot read; pass shuffle_prior_cov='device' for per-episode priors drawn from the "
+                                 "device's Philox streams (vec_env.start_prior: the same distribution, other values)")
             if state != "factor":
                 raise ValueError("budget mode: patch-layout factor engines only (state='factor')")
             if self.field_kind == _ffi.IPP_FIELD_GRF and (cfg.x_dim != cfg.y_dim or cfg.x_dim not in (50, 100)):
@@ -328,6 +364,8 @@ class VecIPPEnv:
             self._started = False
             self.engine.set_budget(self.budget, self.depth, self.episode, self.done, self.refill, self.initial_budget,
                                    self.episode_steps, self.shuffle_budget, self.seed, self.env_id_offset)
+            if self.device_priors:
+                self.engine.set_budget_prior(True)
             if self.feature_history:
                 # NN input history (feature_history = input_history_length): per env a ring of the last H pre-step states, each as
                 # (rank, waypoint, budget / initial budget, episode) -- within an episode the factor columns are only appended, so
@@ -376,13 +414,15 @@ class VecIPPEnv:
             sel = np.nonzero(epi == e)[0].astype(np.int32)
             ids = torch.as_tensor(sel, device=self.device)
             white = self._white[:len(sel)]
+            # (device priors: the pair the reset on done would have installed for this episode)
+            ps = start_prior(self.cfg, self.seed, gid[sel], int(e)) if self.device_priors else None
             if self.field_kind == _ffi.IPP_FIELD_GRF:
                 self.engine.normal_rows(white, self.cfg.n_cells, self.seed, self.GT_STREAM + int(e), row_ids=ids, row_offset=self.env_id_offset)
-                self.engine.reset(env_ids=ids, white_noise=white, prev=self._prev_slots, init_action=INIT_ACTION)
+                self.engine.reset(env_ids=ids, prior_scale=ps, white_noise=white, prev=self._prev_slots, init_action=INIT_ACTION)
             else:
                 self.engine.generate_fields_rows(self.field_kind, len(sel), self.seed, self.GT_STREAM + int(e), white, row_ids=ids,
                                                  row_offset=self.env_id_offset)
-                self.engine.reset(env_ids=ids, gt=white, prev=self._prev_slots, init_action=INIT_ACTION)
+                self.engine.reset(env_ids=ids, prior_scale=ps, gt=white, prev=self._prev_slots, init_action=INIT_ACTION)
             # the next episode's field into the alternate planes: a reset on done flips to it
             self.engine.generate_fields_rows(self.field_kind, len(sel), self.seed, self.GT_STREAM + int(e) + 1, None, row_ids=ids,
                                              row_offset=self.env_id_offset)
@@ -392,6 +432,14 @@ class VecIPPEnv:
         self.done.zero_()
         self.refill.fill_(-1)
         self._started = True
+
+    @property
+    def prior_scale(self):
+        """Prior (sigma^2, l) of every env's current episode, device float64 [num_envs, 2] (IPPEngine.priors; no host sync): the
+        config's pair, or with shuffle_prior_cov="device" start_prior(cfg, seed, global env id, env.episode)."""
+        if self.parts > 1:
+            self.wait()
+        return self.engine.priors()[:self.num_envs]
 
     @staticmethod
     def check_feature_history(feature_history: int, budget) -> None:

@@ -89,6 +89,8 @@ def main():
     ap.add_argument("--steps", type=int, default=12)
     ap.add_argument("--out", default=None)
     ap.add_argument("--planes", choices=["dense", "compact"], default="dense", help="the ring: dense planes or compact rows")
+    ap.add_argument("--shuffle-prior", action="store_true",
+                    help="shuffle_prior_cov: every self-play episode draws its own prior on the device (Learner(episode_priors='device'))")
     a = ap.parse_args()
     import torch
 
@@ -108,6 +110,7 @@ def main():
                 train_examples_history_step=2, max_train_examples_history=10, continuous_network_update=False, num_arena_games=a.envs,
                 network_update_threshold=0.5)
     hp = dict(hp, **net_hp, **train, **loop)
+    hp["shuffle_prior_cov"] = bool(a.shuffle_prior)
     md = dict(md, num_grid_cells=cfg.n_cells)
     torch.manual_seed(0)
     module = PolicyValueNetwork(net_hp, md).to("cuda:0")
@@ -115,13 +118,13 @@ def main():
     with tempfile.TemporaryDirectory() as tmp:
         t0 = time.perf_counter()
         lr = Learner(cfg, a.envs, hp, md, module, tmp, episodes_per_env=a.episodes, capacity=a.envs * slots, sims_in_flight=2,
-                     planes=True if a.planes == "dense" else "compact")
+                     planes=True if a.planes == "dense" else "compact", episode_priors="device" if a.shuffle_prior else None)
         build = time.perf_counter() - t0
         recs = lr.learn()
         sp = lr.selfplay
         cost = commit_cost(sp, a.steps)
         ring = ring_cost(sp, int(hp["batch_size"]))
-        out = dict(ring=ring, envs=a.envs, sims=a.sims, blocks=a.blocks, episodes_per_env=a.episodes, ring_rows=a.envs * slots,
+        out = dict(ring=ring, shuffle_prior=bool(a.shuffle_prior), envs=a.envs, sims=a.sims, blocks=a.blocks, episodes_per_env=a.episodes, ring_rows=a.envs * slots,
                    ring_plane_gib=round(a.envs * slots * 6 * cfg.n_cells ** 2 * 4 / 2 ** 30, 2) if a.planes == "dense" else 0.0, build_s=round(build, 2),
                    iterations=[dict(iteration=r["iteration"], steps=r["totals"]["steps"], examples=r["totals"]["examples"],
                                     window_length=r["window_length"], evicted=r["evicted"],

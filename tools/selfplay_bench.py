@@ -136,6 +136,10 @@ def main():
     ap.add_argument("--per-batch", type=int, default=1024)
     ap.add_argument("--per-reps", type=int, default=20)
     ap.add_argument("--planes", choices=["dense", "compact"], default="dense", help="the small batch's ring: dense planes or compact rows")
+    ap.add_argument("--shuffle-prior", action="store_true",
+                    help="shuffle_prior_cov: every episode draws its own prior on the device (SelfPlay(episode_priors='device'))")
+    ap.add_argument("--window-rows", type=int, default=-1,
+                    help="column window of the envs' engines (-1: the smallest the prior allows; 12 = the shuffled priors' window without them)")
     a = ap.parse_args()
     import torch
 
@@ -144,9 +148,12 @@ def main():
 
     cfg = EngineConfig(x_dim=a.dim, y_dim=a.dim)
     hp, md = params(a.sims, a.episode_steps)
-    sp = SelfPlay(cfg, a.envs, hp, md, planes=False, seed=1)
+    hp["shuffle_prior_cov"] = bool(a.shuffle_prior)
+    kw = dict(episode_priors="device" if a.shuffle_prior else None, window_rows=a.window_rows)
+    sp = SelfPlay(cfg, a.envs, hp, md, planes=False, seed=1, **kw)
     sp.run(a.warmup)
     wall, split = timed(sp, a.steps)
+    window_rows = int(sp.env.engine.info.window_rows)
     ended = int((~torch.isnan(sp.episode_values)).sum().item())
     with_policy = int(sp.last["ok"].sum().item())
     per = per_leg(sp, a.per_batch, a.per_reps)
@@ -155,7 +162,8 @@ def main():
     # the planes phase with planes in the ring (small batch, history 3, cost plane: 16 channels) and 3-step episodes, so that rows are
     # committed and one minibatch with one augmented copy is gathered (ipp_replay_gather)
     hp3, md3 = params(a.sims, 3)
-    small = SelfPlay(cfg, a.planes_envs, hp3, md3, planes=True if a.planes == "dense" else "compact", seed=1)
+    hp3["shuffle_prior_cov"] = bool(a.shuffle_prior)
+    small = SelfPlay(cfg, a.planes_envs, hp3, md3, planes=True if a.planes == "dense" else "compact", seed=1, **kw)
     small.run(1)
     _, split_small = timed(small, 3)
     small.replay.timing = []
@@ -167,11 +175,13 @@ def main():
     ring = ring_leg(small, a.batch)
     small.close()
     split["planes"] = "not measured: the 4096-env batch keeps no planes (planes=False); see planes_ms_small_batch"
-    out = {"envs": a.envs, "grid": a.dim, "sims": a.sims, "steps": a.steps, "samples_per_s": a.envs * a.steps / wall,
+    out = {"envs": a.envs, "grid": a.dim, "sims": a.sims, "steps": a.steps, "shuffle_prior": bool(a.shuffle_prior), "window_rows": window_rows,
+           "samples_per_s": a.envs * a.steps / wall,
            "step_ms": 1e3 * wall / a.steps, "split_ms": split, "episodes_ended_last_step": ended,
            "roots_with_policy_last_step": with_policy, "gather_kernel_ms_small_batch": gather_ms, "gathered_rows": gathered_rows,
            "prioritised_replay": per, "ring": ring,
-           "planes_ms_small_batch": {"envs": a.planes_envs, "planes": split_small["planes"], "record": split_small["record"]}}
+           "planes_ms_small_batch": {"envs": a.planes_envs, "planes": split_small["planes"], "record": split_small["record"],
+                                     "step": split_small["step"]}}  # (3-step episodes: these steps reset envs)
     print(json.dumps(out))
 
 

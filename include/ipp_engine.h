@@ -688,6 +688,73 @@ int ipp_set_adaptive(void* engine, double value_threshold, double interval_facto
 int ipp_fork(void* engine, const int32_t* src_ids /*[dev]*/, const int32_t* dst_ids /*[dev]*/, int32_t n,
              void* stream);
 
+/*
+ * Slot export and import (csrc/k_slots.h, csrc/ipp_slots.hip): the state of env slots of a patch-layout factor engine
+ * (ipp_info.patch_layout == 1) as packed records in caller memory, and back into any slots of an engine with the same layout
+ * fingerprint -- the same engine, or another one on the same device whose capacity, rank_cap and max_batch may differ.  The factor
+ * columns U have no other way out of an engine (ipp_read_cov_dense gives the N x N matrix, ipp_write_cov_dense refuses factor
+ * engines, ipp_fork stays inside one engine).  No reference counterpart: the reference pickles its dense grid maps.  Added without
+ * an ABI bump: no existing struct or call changes.
+ *
+ * A record is its header followed by the sections `what` selects, in this order; every part starts on a 16-byte boundary (its
+ * length is rounded up to 16 bytes, the padding is zero), so any N works.  r = the record's rank, pad16(b) = b rounded up to 16:
+ *
+ *   part      bytes                 content
+ *   --------  --------------------  -----------------------------------------------------------------------------------------
+ *   header    32                    uint32 magic IPP_SLOT_MAGIC, uint32 format IPP_SLOT_FORMAT, uint32 what, int32 r (the slot's
+ *                                   rank clamped to [0, rank_cap] with IPP_SLOT_COLUMNS, else 0), uint64 bytes of the whole
+ *                                   record, int32 N, int32 pstride.  A slot id outside the engine exports a header alone: what = 0
+ *   IPP_SLOT_COLUMNS
+ *     prior   16                    double sigma^2, double l: the slot's prior pair
+ *     colspan pad16(4 r)            int32 [r]: View::colspan[0 .. r)
+ *     colrect pad16(4 r)            int32 [r]: View::colrect[0 .. r)
+ *     columns 4 r pstride           float [r][pstride]: the stored patches (pstride is a multiple of 16 floats)
+ *   IPP_SLOT_MAPS
+ *     mean    pad16(4 N)            float [N]
+ *     diag    pad16(4 N)            float [N]: the stored diagonal
+ *     gt      pad16(4 N)            float [N]: the slot's CURRENT ground-truth plane; a staged next-episode field is not carried
+ *
+ * Import of IPP_SLOT_COLUMNS writes the rank, the prior pair, colspan, colrect and the columns [0, r); of IPP_SLOT_MAPS the mean, the
+ * diagonal and the ground truth into plane e of slot e, with gt_slot[e] = e and the staged flag gt_slot[capacity + e] = 0.  The
+ * kernels move 16 bytes per lane and access and use vector stores only; grid (chunks, n) like ipp_fork, the workgroups of a slot
+ * indexed by its rank (a chunk behind the slot's last column exits).  Nothing inside the calls reads the device from the host.
+ * status [dev] int32[n]: IPP_SLOT_OK; IPP_SLOT_BAD_ID: id outside [0, capacity); IPP_SLOT_RANK (import): the record's rank exceeds
+ * this engine's rank_cap; IPP_SLOT_BAD_RECORD (import): the bytes at offsets[i] are not a record of this `what`, N and pstride that
+ * ends at offsets[i + 1], or offsets[i] is not a multiple of 16.  An imported slot whose status is not 0 is left bit for bit as it was.
+ * Duplicate DESTINATION ids in one ipp_slots_import are undefined (two workgroups write one slot); duplicate ids in plan / export are
+ * fine.  blob: [dev], 16-byte aligned.  Refused (-1, nothing launched): dense engines, factor engines without the patch layout, a NULL
+ * argument, n < 0, what == 0 or with unknown bits.
+ */
+#define IPP_SLOT_COLUMNS 1u
+#define IPP_SLOT_MAPS    2u
+#define IPP_SLOT_FORMAT  1
+#define IPP_SLOT_MAGIC   0x4c535049u /* "IPSL" */
+#define IPP_SLOT_HEADER_BYTES 32
+#define IPP_SLOT_OK         0
+#define IPP_SLOT_BAD_ID     1
+#define IPP_SLOT_RANK       2
+#define IPP_SLOT_BAD_RECORD 3
+/* What a packed record depends on.  Two engines exchange slots if and only if every field is equal. */
+typedef struct ipp_slot_layout {
+    int32_t format;                 /* IPP_SLOT_FORMAT */
+    int32_t W, H, N, Npad;          /* grid and its padded cell count */
+    int32_t pw, ph, pstride;        /* patch width, height, floats per stored column */
+    int32_t window_rows, tile_cells;
+    int32_t prior_kind;             /* IPP_PRIOR_* */
+    int32_t reserved;               /* 0 */
+} ipp_slot_layout;
+int ipp_slots_layout(void* engine, ipp_slot_layout* out /*[host]*/); /* (host only; the call's name is the plural: the type has the other) */
+/* offsets[i] = the sum of the record sizes of slot_ids[0 .. i), each a function of the slot's rank read on the device (one workgroup,
+ * an exclusive scan); offsets[n] = the bytes of the blob, the one value the caller reads.  status as above. */
+int ipp_slots_plan(void* engine, const int32_t* slot_ids /*[dev]*/, int32_t n, uint32_t what, uint64_t* offsets /*[dev] [n + 1]*/,
+                   int32_t* status /*[dev] [n]*/, void* stream);
+/* The record of slot_ids[i] at blob + offsets[i] (ipp_slots_plan's, on the same stream, no step in between). */
+int ipp_slots_export(void* engine, const int32_t* slot_ids /*[dev]*/, int32_t n, uint32_t what, const uint64_t* offsets /*[dev]*/,
+                     void* blob /*[dev]*/, void* stream);
+/* The inverse: the record at blob + offsets[i] into slot slot_ids[i]. */
+int ipp_slots_import(void* engine, const int32_t* slot_ids /*[dev]*/, int32_t n, uint32_t what, const uint64_t* offsets /*[dev] [n + 1]*/,
+                     const void* blob /*[dev]*/, int32_t* status /*[dev] [n]*/, void* stream);
+
 /* Materialise per-env state for callers / tests (reference: grid_map.mean, np.diag(cov_matrix),
  * cov_matrix, sensor_simulation.ground_truth_map; planning/missions.py:176-203). out is [dev]. */
 int ipp_read_mean(void* engine, int32_t env_id, float* out /*[N]*/, void* stream);

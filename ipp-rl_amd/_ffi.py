@@ -140,6 +140,19 @@ class IppReplayCompact(C.Structure):
     ]
 
 
+IPP_SLOT_COLUMNS, IPP_SLOT_MAPS = 1, 2
+IPP_SLOT_OK, IPP_SLOT_BAD_ID, IPP_SLOT_RANK, IPP_SLOT_BAD_RECORD = 0, 1, 2, 3
+
+
+class IppSlotLayout(C.Structure):
+    """ipp_slot_layout (include/ipp_engine.h): what a packed slot record depends on; engines exchange slots iff every field is equal."""
+    _fields_ = [
+        ("format", C.c_int32), ("W", C.c_int32), ("H", C.c_int32), ("N", C.c_int32), ("Npad", C.c_int32),
+        ("pw", C.c_int32), ("ph", C.c_int32), ("pstride", C.c_int32), ("window_rows", C.c_int32), ("tile_cells", C.c_int32),
+        ("prior_kind", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 class IppIterTotals(C.Structure):
     """The 32-byte record of ipp_selfplay_iter_totals."""
     _fields_ = [("episodes_kept", C.c_int64), ("envs_at_cap", C.c_int64), ("examples", C.c_int64), ("value_sum", C.c_double)]
@@ -254,6 +267,11 @@ PROTOTYPES = {
     "ipp_set_item_order": (C.c_int, [_P, _P, C.c_int32]),
     "ipp_set_reset_prior": (C.c_int, [_P, _P]),
     "ipp_fork": (C.c_int, [_P, _P, _P, C.c_int32, _P]),
+    # (slot export and import, csrc/k_slots.h: added without an ABI bump, nothing existing changes layout)
+    "ipp_slots_layout": (C.c_int, [_P, C.POINTER(IppSlotLayout)]),
+    "ipp_slots_plan": (C.c_int, [_P, _P, C.c_int32, C.c_uint32, _P, _P, _P]),
+    "ipp_slots_export": (C.c_int, [_P, _P, C.c_int32, C.c_uint32, _P, _P, _P]),
+    "ipp_slots_import": (C.c_int, [_P, _P, C.c_int32, C.c_uint32, _P, _P, _P, _P]),
     "ipp_read_mean": (C.c_int, [_P, C.c_int32, _P, _P]),
     "ipp_read_diag": (C.c_int, [_P, C.c_int32, _P, _P]),
     "ipp_read_gt": (C.c_int, [_P, C.c_int32, _P, _P]),

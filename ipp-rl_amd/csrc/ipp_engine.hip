@@ -1514,6 +1514,16 @@ int ipp::factor_slots(void* engine, FactorSlots* out) {
     return 0;
 }
 
+int ipp::slot_store(void* engine, SlotStore* out) {
+    const Engine* e = as_engine(engine);
+    if (!e) return fail(-1, "null engine");
+    const View& v = e->v;
+    *out = SlotStore{e->device, v.mode, v.cap, v.rank_cap, v.W, v.H, v.N, v.Npad, v.pw, v.ph, v.pstride, v.window_rows, v.tile_cells,
+                     v.prior_kind, e->patch && v.mode == IPP_FACTOR, v.cov_slot, v.cov, v.colspan, v.colrect, v.rank, v.prior,
+                     v.mean, v.diag, v.gt, v.gt_slot};
+    return 0;
+}
+
 int ipp::tree_step(void* engine, const int32_t* root_ids, const int32_t* path_ids, const int32_t* new_ids, int32_t n, const double* action,
                    const double* prev_action, uint32_t flags, float* reward, int32_t* status, void* stream, const int32_t* n_dev,
                    const TreeEdgeOut* edge_out) {

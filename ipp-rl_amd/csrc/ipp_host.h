@@ -1,5 +1,5 @@
-// Host-side internals shared by the library's six translation units: the one error slot behind ipp_last_error, and the narrow view
-// of an engine that the search calls (ipp_search.hip) need.  No kernels.
+// Host-side internals shared by the library's seven translation units: the one error slot behind ipp_last_error, and the narrow views
+// of an engine that the search calls (ipp_search.hip) and the slot calls (ipp_slots.hip) need.  No kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -35,6 +35,18 @@ struct FactorSlots {
     const int* led_depth; const long long* led_episode;
 };
 int factor_slots(void* engine, FactorSlots* out);  // (null engine: "null engine")
+
+// Everything of an engine's env slots that a packed slot record holds (k_slots.h, ipp_slots.hip): the geometry the record's layout
+// depends on and the slabs of View.  A struct of its own, passed to the slot kernels by value: View and FactorSlots stay as they are.
+struct SlotStore {
+    int device, mode, cap, rank_cap;
+    int W, H, N, Npad, pw, ph, pstride, window_rows, tile_cells, prior_kind;
+    bool patch;
+    uint64_t cov_slot;  // floats per slot
+    float* cov; int* colspan; int* colrect; int* rank; double* prior;
+    float* mean; float* diag; float* gt; int* gt_slot;
+};
+int slot_store(void* engine, SlotStore* out);  // (null engine: "null engine")
 
 // ipp_tree_step + the search driver's extras: the item count on the device (n_dev), the edge numerators written by the patch kernel
 // itself (edge_out: ipp_common.h); either may be NULL

@@ -17,6 +17,7 @@ from typing import Dict, Optional
 import numpy as np
 
 from . import _ffi
+from . import slots as slots_format
 
 
 @dataclass
@@ -872,6 +873,74 @@ class IPPEngine:
         s, d = self._dev(src_ids, torch.int32), self._dev(dst_ids, torch.int32)
         _ffi.check(self._lib.ipp_fork(self._h, self._ptr(s), self._ptr(d), int(s.numel()), self.stream))
         self._keep = (s, d)
+
+    # ------------------------------------------------------------------ slot export / import (csrc/k_slots.h, slots.py)
+    def slot_layout(self) -> Dict:
+        """The fingerprint a packed slot record depends on (ipp_slot_layout) as a plain dict; engines exchange slots iff theirs are
+        equal (capacity, rank_cap and max_batch may differ).  Dense and non-patch factor engines raise IppError."""
+        lay = _ffi.IppSlotLayout()
+        _ffi.check(self._lib.ipp_slots_layout(self._h, C.byref(lay)))
+        return {k: int(getattr(lay, k)) for k in slots_format.LAYOUT_FIELDS}
+
+    def export_slots(self, slot_ids, columns: bool = True, maps: bool = True) -> Dict:
+        """The named slots as packed records (include/ipp_engine.h "Slot export and import"): dict(layout, what, offsets int64 [n + 1],
+        blob uint8, status int32 [n]; the tensors on the device -- .cpu() them for torch.save).  columns: rank, prior pair, spans,
+        rectangles and the stored patches; maps: mean, diagonal, current ground truth.  One host read: the blob's size."""
+        torch = _torch()
+        what = (_ffi.IPP_SLOT_COLUMNS if columns else 0) | (_ffi.IPP_SLOT_MAPS if maps else 0)
+        layout = self.slot_layout()
+        ids = self._dev(slot_ids, torch.int32).reshape(-1)
+        n = int(ids.numel())
+        offsets = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+        status = torch.zeros(n, dtype=torch.int32, device=self.device)
+        if n == 0:  # (no slot: no record, nothing to launch)
+            if what == 0:
+                raise ValueError("export_slots: columns=False and maps=False select no section")
+            return dict(layout=layout, what=int(what), offsets=offsets, blob=torch.empty(0, dtype=torch.uint8, device=self.device), status=status)
+        _ffi.check(self._lib.ipp_slots_plan(self._h, self._ptr(ids), n, what, self._ptr(offsets), self._ptr(status), self.stream))
+        total = int(offsets[n].item())  # (the one read)
+        blob = torch.empty(total, dtype=torch.uint8, device=self.device)
+        _ffi.check(self._lib.ipp_slots_export(self._h, self._ptr(ids), n, what, self._ptr(offsets), self._ptr(blob), self.stream))
+        self._keep = (ids,)
+        return dict(layout=layout, what=int(what), offsets=offsets, blob=blob, status=status)
+
+    def import_slots(self, slot_ids, packed: Dict, check: bool = True):
+        """The records of `packed` (export_slots of an engine with an equal layout, on any device or the host) into the named slots, record i
+        into slot_ids[i]; duplicate ids are undefined.  ValueError before any launch: another fingerprint or format version (the field
+        is named), a record count other than the ids', offsets outside the blob.  Returns the status tensor (0 ok, 1 id outside the
+        engine, 2 the record's rank exceeds this rank_cap, 3 not a record; a slot with a status is left as it was); check=True reads it
+        and raises ValueError on the first non-zero entry."""
+        torch = _torch()
+        slots_format.check_layouts(self.slot_layout(), packed["layout"])
+        what = slots_format.check_what(packed["what"])
+        ids = self._dev(slot_ids, torch.int32).reshape(-1)
+        n = int(ids.numel())
+        offs_host = torch.as_tensor(packed["offsets"]).to("cpu", torch.int64).reshape(-1)
+        blob = packed["blob"]
+        nbytes = int(blob.numel())
+        if int(offs_host.numel()) != n + 1:
+            raise ValueError(f"{int(offs_host.numel()) - 1} packed records for {n} slot ids")
+        if n and (int(offs_host.min()) < 0 or int(offs_host.max()) > nbytes or bool((offs_host[1:] < offs_host[:-1]).any())):
+            raise ValueError(f"the packed slots' offsets do not ascend inside the blob of {nbytes} bytes")
+        offsets = offs_host.to(self.device)
+        blob = torch.as_tensor(blob).to(device=self.device, dtype=torch.uint8).contiguous()
+        if blob.data_ptr() % 16:  # (a view into a larger tensor)
+            blob = blob.clone()
+        status = torch.zeros(n, dtype=torch.int32, device=self.device)
+        if n == 0:
+            return status
+        _ffi.check(self._lib.ipp_slots_import(self._h, self._ptr(ids), n, what, self._ptr(offsets), self._ptr(blob), self._ptr(status),
+                                              self.stream))
+        self._keep = (ids, offsets, blob)
+        if check:
+            st = status.cpu()
+            bad = torch.nonzero(st).reshape(-1)
+            if bad.numel():
+                i = int(bad[0])
+                why = {1: "the id is outside the engine", 2: f"the record's rank exceeds rank_cap = {self.rank_cap}",
+                       3: "the bytes are not a record of this layout"}.get(int(st[i]), "unknown status")
+                raise ValueError(f"import_slots: slot {int(ids[i].item())} (record {i}) has status {int(st[i])}: {why}")
+        return status
 
     def _read(self, fn, env, numel):
         torch = _torch()

@@ -20,8 +20,10 @@ network_wrappers/policy_value_network_wrappers.py:233-249) in `checkpoint_dir`; 
 iteration, the scheduled values, prev_network_wins, the rows each iteration reported and the draws' seeds and counters.
 
 Divergences from the reference (INTEGRATION.md "Learn loop"): episodes per env, not per worker; an env's episodes past its share are
-played out and dropped; an iteration abandons the running episodes; the ring is not persisted (a resumed loop starts with an empty
-window); shared_network=False, skip_first_self_play / train_examples_iter, TensorBoard and Telegram are not provided.
+played out and dropped; an iteration abandons the running episodes; the ring is persisted only on request (persist_replay=True writes
+replay_state.pt, and a resumed loop trains on the full off-policy window as the reference's does from its sample files; by default a
+resumed loop starts with an empty window); the running episodes and their pending rows are abandoned at a resume either way;
+shared_network=False, skip_first_self_play / train_examples_iter, TensorBoard and Telegram are not provided.
 """
 from __future__ import annotations
 
@@ -32,6 +34,7 @@ from typing import Callable, Dict, List, Optional, Tuple
 
 TEMP_FILE = "shared_net.temp.pth.tar"
 STATE_FILE = "learn_state.pt"
+REPLAY_FILE = "replay_state.pt"
 
 
 def snapshot_file(iteration: int) -> str:
@@ -86,12 +89,15 @@ class Learner:
     def __init__(self, cfg, num_envs: int, hyper_params: Dict, meta_data: Dict, module, checkpoint_dir: str,
                  episodes_per_env: Optional[int] = None, arena_envs: Optional[int] = None, seed: int = 0, env_id_offset: int = 0,
                  deployment_filename: str = "trained_model.pth.tar", precision: str = "fp32", net_max_batch: Optional[int] = None,
-                 **selfplay_kwargs):
+                 persist_replay: bool = False, **selfplay_kwargs):
         """cfg: EngineConfig; hyper_params / meta_data: the reference's dictionaries (config/example.yaml) for the search, the network
         and the trainer in one, as there; module: the PolicyValueNetwork to train, on the device.  episodes_per_env: episodes every env
         ends per iteration (default ceil(num_episodes x num_workers / num_envs): at least the reference's episodes per iteration).
         arena_envs: envs of the gate's arena (default gcd(num_arena_games, num_envs)).  net_max_batch: leaves one forward of a device
-        network takes (default max(num_envs, arena_envs) x sims_in_flight).  selfplay_kwargs go to SelfPlay (capacity: the ring has to
+        network takes (default max(num_envs, arena_envs) x sims_in_flight).  persist_replay: every finished iteration also writes the ring
+        (SelfPlay.state_dict: row arrays, archive bookkeeping and, for a compact ring, the archived episodes' columns, tensors on the
+        host) to replay_state.pt, and learn(resume=True) loads it back, so the resumed iterations train on the whole off-policy window;
+        planes="compact" rings only here (a dense-planes ring raises at the first save).  selfplay_kwargs go to SelfPlay (capacity: the ring has to
         hold the rows of a whole off-policy window, see INTEGRATION.md "Learn loop"; planes="compact" and archive_episodes: the compact
         ring, whose rows are a few KB, so that such a window fits beside thousands of envs; episode_priors="device": a true
         hyper_params["shuffle_prior_cov"] -- config/example.yaml's setting -- gives every self-play episode its own prior, drawn on the
@@ -114,6 +120,7 @@ class Learner:
         self.seed, self.env_id_offset = int(seed), int(env_id_offset)
         self.puct_init, self.dirichlet_alpha = float(hp["puct_init"]), float(hp["dirichlet_alpha"])
         self.prev_network_wins = 0
+        self.persist_replay = bool(persist_replay)
         self.iteration = -1         # the last finished iteration
         self.reported: Dict[int, int] = {}  # iteration -> rows its self-play reported (for `evicted`)
         self.history: List[Dict] = []
@@ -149,7 +156,37 @@ class Learner:
         ckpt = self.torch.load(self._path(name), map_location=next(self.module.parameters()).device)
         self.module.load_state_dict(ckpt["state_dict"], strict=True)
 
+    def _save_replay(self):
+        """replay_state.pt: the ring's state dict with its tensors on the host, and the iteration it belongs to.  Written to a temporary
+        name and moved into place, BEFORE learn_state.pt: a learn_state.pt never names an iteration whose ring is not on disk."""
+        torch = self.torch
+
+        def to_host(x):
+            if isinstance(x, torch.Tensor):
+                return x.cpu()
+            if isinstance(x, dict):
+                return {k: to_host(v) for k, v in x.items()}
+            return x
+
+        os.makedirs(self.checkpoint_dir, exist_ok=True)
+        tmp = self._path(REPLAY_FILE + ".tmp")
+        torch.save(dict(iteration=int(self.iteration), replay=to_host(self.selfplay.state_dict())), tmp)
+        os.replace(tmp, self._path(REPLAY_FILE))
+
+    def _load_replay(self):
+        path = self._path(REPLAY_FILE)
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"persist_replay=True: {path} is missing ({REPLAY_FILE} is written beside {STATE_FILE} by a Learner "
+                                    f"with persist_replay=True)")
+        st = self.torch.load(path, map_location="cpu")
+        if int(st["iteration"]) != self.iteration:
+            raise ValueError(f"{REPLAY_FILE} holds the ring behind iteration {int(st['iteration'])}, {STATE_FILE} names iteration "
+                             f"{self.iteration}")
+        self.selfplay.load_state_dict(st["replay"])
+
     def _save_state(self):
+        if self.persist_replay:
+            self._save_replay()
         env = self.selfplay.env
         self.torch.save(dict(iteration=self.iteration, puct_init=self.puct_init, dirichlet_alpha=self.dirichlet_alpha,
                              prev_network_wins=self.prev_network_wins, reported=dict(self.reported), seed=self.seed,
@@ -159,7 +196,8 @@ class Learner:
     def _resume(self):
         """Continue behind the last finished iteration: the schedules as they were applied, the deployed weights in the module and both
         device networks, the envs' episode counters and the ring's draw count (no episode and no minibatch draw comes twice).  The
-        ring itself is not persisted."""
+        ring itself comes back only with persist_replay=True (replay_state.pt: a missing file or one of another iteration raises);
+        otherwise the window starts empty.  Running episodes and pending rows are abandoned either way."""
         st = self.torch.load(self._path(STATE_FILE), map_location="cpu")
         if int(st["seed"]) != self.seed or int(st["env_id_offset"]) != self.env_id_offset:
             raise ValueError(f"learn_state.pt was written with seed {int(st['seed'])}, env_id_offset {int(st['env_id_offset'])}")
@@ -174,6 +212,8 @@ class Learner:
         if tuple(st["episode"].shape) != tuple(env.episode.shape):
             raise ValueError(f"learn_state.pt holds {int(st['episode'].numel())} envs, this Learner {self.num_envs}")
         env.episode.copy_(st["episode"].to(env.episode.device))  # (begin_iteration's reset starts the episodes behind these)
+        if self.persist_replay:
+            self._load_replay()
         self.selfplay.replay.draws = int(st["replay_draws"])
 
     # ------------------------------------------------------------------ one iteration

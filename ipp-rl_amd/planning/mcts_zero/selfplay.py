@@ -308,6 +308,20 @@ def archive_slot(num_envs: int, archive_episodes: int, env, episode):
     return int(num_envs) + np.asarray(env, dtype=np.int64) * int(archive_episodes) + np.asarray(episode, dtype=np.int64) % int(archive_episodes)
 
 
+def archive_slots_in_use(episodes, num_envs: int, archive_episodes: int) -> np.ndarray:
+    """Ascending engine slots of a compact ring that hold an archived episode: slot num_envs + e E + j does iff j < min(E, episodes[e])
+    (env e has archived episodes[e] episodes, episode p into place p mod E).  What a ring's state_dict exports, from one read of
+    `episodes`."""
+    epi = np.asarray(episodes, dtype=np.int64).reshape(-1)
+    B, E = int(num_envs), int(archive_episodes)
+    if len(epi) != B:
+        raise ValueError(f"{len(epi)} episode counters for {B} envs")
+    j = np.arange(E, dtype=np.int64)[None, :]
+    used = j < np.minimum(epi, E)[:, None]
+    slots = B + np.arange(B, dtype=np.int64)[:, None] * E + j
+    return slots[used].astype(np.int64)
+
+
 def eviction_host(trace, slots: int, archive_episodes: int):
     """ipp_selfplay_archive's eviction and the ring's committed rows on a host trace of ONE env: trace[t] = (episode tag of the env's
     running episode at step t, recorded: the step left a sample, ended: the episode ended in step t).  Row t mod S takes the sample of
@@ -398,6 +412,66 @@ class ReplayBuffer:
     def evicted(self) -> int:
         """Rows that lost their flag because the archive slot of their episode was reused (compact mode; reads the device)."""
         return int(self._evicted.item()) if self.compact is not None else 0
+
+    # ------------------------------------------------------------------ persistence
+    _ROW_ARRAYS = ("policy", "idx", "value", "reward", "flags", "iter")
+    _COMPACT_ARRAYS = ("entries", "mean", "episode_tag", "episodes", "last_rank")
+
+    def geometry(self) -> Dict:
+        """What two rings have to share to exchange a state_dict."""
+        c = self.compact is not None
+        return dict(slots=self.slots, num_envs=self.num_envs, kmax=self.kmax, num_actions=self.num_actions, side=self.side,
+                    history=self.history if c else 0, E=self.archive_episodes if c else 0, compact=bool(c))
+
+    def state_dict(self) -> Dict:
+        """Everything of a compact or planes=False ring a later process needs to go on sampling it: the row arrays (compact: entries,
+        mean, episode tag; policy, idx, value, reward, flags, iter), the archive bookkeeping (episodes, last_rank, evicted), the draw
+        count, the loop's step counter (the ring position), the geometry and, for a compact ring, the columns of exactly the archive
+        slots that hold an episode (IPPEngine.export_slots, columns only; archive_slots_in_use from one read of `episodes`).  Tensors
+        stay on the device.  The running episodes are not part of it: load_state_dict drops their pending rows.  A dense-planes ring
+        raises ValueError."""
+        if self.planes is not None:
+            raise ValueError(f"a dense-planes ring is not persisted: its planes alone are {self.planes.numel() * 4 / 2**30:.2f} GiB "
+                             f"({self.capacity} rows of {self.channels} x {self.side}^2 floats); use planes='compact'")
+        sd = dict(geometry=self.geometry(), draws=int(self.draws), step=int(self._owner.t))
+        for name in self._ROW_ARRAYS:
+            sd[name] = getattr(self, name).clone()
+        if self.compact is not None:
+            for name in self._COMPACT_ARRAYS:
+                sd[name] = getattr(self, name).clone()
+            sd["evicted"] = self._evicted.clone()
+            used = archive_slots_in_use(self.episodes.cpu().numpy(), self.num_envs, self.archive_episodes)
+            sd["archive_slots"] = self.torch.as_tensor(used, dtype=self.torch.int64)
+            sd["archive"] = self._owner.env.engine.export_slots(used, columns=True, maps=False)
+        return sd
+
+    def load_state_dict(self, sd: Dict):
+        """state_dict of a ring of the same geometry (ValueError names a mismatch), from any device or the host: the arrays, the archive
+        slots into the owner's engine (IPPEngine.import_slots: ValueError for another slot layout), the draw count and the step counter.
+        Every PENDING row becomes 0: the running episodes are not part of a checkpoint."""
+        torch = self.torch
+        if self.planes is not None:
+            raise ValueError("a dense-planes ring is not persisted; use planes='compact'")
+        mine, theirs = self.geometry(), dict(sd["geometry"])
+        for k, v in mine.items():
+            if k not in theirs or theirs[k] != v:
+                raise ValueError(f"replay state of another ring: {k} = {theirs.get(k)!r}, this ring has {v!r}")
+        names = self._ROW_ARRAYS + (self._COMPACT_ARRAYS if self.compact is not None else ())
+        for name in names:
+            dst, src = getattr(self, name), sd[name]
+            if tuple(src.shape) != tuple(dst.shape) or src.dtype != dst.dtype:
+                raise ValueError(f"replay state: {name} is {tuple(src.shape)} {src.dtype}, this ring has {tuple(dst.shape)} {dst.dtype}")
+        if self.compact is not None:
+            used = archive_slots_in_use(sd["episodes"].cpu().numpy(), self.num_envs, self.archive_episodes)
+            if not np.array_equal(used, sd["archive_slots"].cpu().numpy()):
+                raise ValueError("replay state: the exported archive slots are not those its episode counters name")
+            self._owner.env.engine.import_slots(used, sd["archive"], check=True)
+            self._evicted.copy_(sd["evicted"].to(self._evicted.device))
+        for name in names:
+            getattr(self, name).copy_(sd[name].to(self.flags.device))
+        self.flags[self.flags == PENDING] = 0
+        self.draws = int(sd["draws"])
+        self._owner.t = int(sd["step"])
 
     def _compact_planes(self, n: int, copies: int, index, offsets, states):
         """states [n copies, C, N, N] of a minibatch drawn with channels = 0 (ipp_replay_compact_planes)."""
@@ -837,6 +911,18 @@ class SelfPlay:
             self.step_iteration()
             steps += 1
         return dict(self.iteration_totals, steps=steps)
+
+    # ------------------------------------------------------------------ persistence of the ring
+    def state_dict(self) -> Dict:
+        """ReplayBuffer.state_dict of the loop's ring (compact or planes=False; tensors on the device)."""
+        return self.replay.state_dict()
+
+    def load_state_dict(self, sd: Dict):
+        """ReplayBuffer.load_state_dict into the loop's ring.  A loop that has already stepped abandons its running episodes first
+        (reset()), as an iteration does; their pending rows, like the checkpoint's, are dropped."""
+        if self.t:
+            self.reset()
+        self.replay.load_state_dict(sd)
 
     def close(self):
         self.env.engine.close()

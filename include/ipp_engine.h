@@ -216,6 +216,21 @@ int ipp_engine_info(void* engine, ipp_info* out /*[host]*/);
 #define IPP_GRF_GEN_HARTLEY 2 /* four fp64 GEMMs with the Hartley matrix (k_grf_hartley.h) */
 #define IPP_GRF_GEN_FFT 3     /* fast Hartley transforms in LDS, draws its own noise (k_grf_fft.h) */
 int ipp_grf_generator(void* engine, int32_t* kind /*[host]*/, int32_t* param /*[host]*/);
+/*
+ * Which grids the generators that draw their own white noise serve: ipp_generate_grf_rows / _groups / _refill, and
+ * ipp_generate_field_groups / _refill with IPP_FIELD_GRF.
+ *   all_grids = 0  (the default) only where the engine runs k_grf_fft (50x50 and 100x100 grids): -3 elsewhere, as without the call.
+ *   all_grids = 1  every even square grid of 4 .. 256 cells a side, through whichever family ipp_grf_generator names for this engine
+ *                  (the IPP_GRF_HARTLEY / IPP_GRF_FFT switches still choose it): the GEMM-Hartley kernels and the 256-thread DFT kernels
+ *                  draw the noise into the LDS array they staged it in; the 1024-thread DFT kernels (n > 128, or n > 100 without the
+ *                  Hartley form) keep it in the field's own destination until the field overwrites it.  Same noise definition, so
+ *                  a field is the same bits as ipp_fill_normal_rows + ipp_generate_grf on that engine.  Accepted and without effect
+ *                  on 50x50 / 100x100.  No scratch is added: the engine's arena is the one it has without the call.
+ * Returns -1 (naming the grid and the rule) with all_grids = 1 on a grid the rule excludes: odd, non-square, above 256.
+ * Budget-mode drivers need it for Gaussian random fields on any grid but the two above: a budget step's refill list lives on the
+ * device, and only a generator that draws its own noise can serve it without a host read.
+ */
+int ipp_set_grf_rows(void* engine, int32_t all_grids);
 
 /*
  * Episode reset of `n` env slots: mean <- 0.5, covariance <- prior, rank <- 0, ground truth <- gt / GRF.
@@ -307,7 +322,8 @@ int ipp_set_reset_prior(void* engine, const double* prior);
  *                                   Philox uniform of counter (env + row_offset), subsequence IPP_BUDGET_STREAM + episode, key seed
  *   max_steps                       max_episode_steps
  * A reset on done is ipp_step_autoreset's flip to the alternate ground-truth plane (reset_gt == NULL): mean 0.5, the config's prior
- * (or the new episode's own: ipp_set_budget_prior), rank 0, prev_action[env] <- init_action; ipp_generate_grf_refill stages the next field behind every such step.
+ * (or the new episode's own: ipp_set_budget_prior), rank 0, prev_action[env] <- init_action; ipp_generate_grf_refill stages the next field behind every such step
+ * (Gaussian random fields: 50x50 / 100x100 grids, or any even square grid up to 256 after ipp_set_grf_rows(engine, 1)).
  */
 int ipp_set_budget(void* engine, double* budget, int32_t* depth, int64_t* episode, uint8_t* done, int32_t* refill,
                    double initial_budget, int32_t max_steps, int32_t shuffle_budget, uint64_t seed, int64_t row_offset);
@@ -575,7 +591,8 @@ int ipp_generate_grf(void* engine, int32_t n, const float* white_noise /*[dev]*/
  * The same with the white noise drawn inside the generator: field i gets exactly the numbers
  * ipp_fill_normal_rows(out, 1, n, H * W, row_ids, row_offset, seed, subsequence) would have put into row i (so a ground truth does
  * not depend on which of the two routes made it), without the H * W floats per field written and read back.  Only where
- * the engine has such a generator (50x50 and 100x100 grids: k_grf_fft.h); returns -3 elsewhere (use the two calls).
+ * the engine has such a generator (50x50 and 100x100 grids: k_grf_fft.h; every even square grid of 4 .. 256 cells a side after
+ * ipp_set_grf_rows(engine, 1)); returns -3 elsewhere (use the two calls).
  *   row_ids [dev] int32[n] or NULL (row i)
  */
 int ipp_generate_grf_rows(void* engine, int32_t n, const int32_t* row_ids, int64_t row_offset, uint64_t seed, uint64_t subsequence,
@@ -588,6 +605,8 @@ int ipp_generate_grf_rows(void* engine, int32_t n, const int32_t* row_ids, int64
  * current one and the one for its next episode; a reset folded into a step launch with reset_gt == NULL (ipp_step_autoreset,
  * ipp_step_parts) then only flips the env to it instead of copying H * W floats in and out (at 100x100 and 2048 resets per step the
  * copies were 164 MB of a step's traffic).  ipp_read_gt / ipp_write_gt / ipp_reset always address the CURRENT plane.
+ * The env slots named in one such launch are distinct (two fields for one plane would race; after ipp_set_grf_rows the 1024-thread DFT
+ * kernels also keep a field's noise in its destination while they work).  Same grids as ipp_generate_grf_rows (-3 elsewhere).
  * simulations/ground_truths.py:14-33 (the field), mapping/mappings.py:217-261 (the reset that installs it). */
 int ipp_generate_grf_groups(void* engine, int32_t n, int32_t group_rows, const int64_t* group_subsequence /*[host] or NULL*/,
                             const int32_t* row_ids /*[dev] or NULL*/, int64_t row_offset, uint64_t seed, uint64_t subsequence,
@@ -596,7 +615,7 @@ int ipp_generate_grf_groups(void* engine, int32_t n, int32_t group_rows, const i
  * refill[i] (a negative entry skips the field) and sets its staged flag; its noise is drawn from subsequence + episode[env] + 1 --
  * the field of the episode after the one that env has just started, so that a one-step episode finds its next field staged.  Launch
  * it behind the step on the step's stream, over the n positions of the launch (or over one part's position range on that part's
- * stream).  Same grids as ipp_generate_grf_rows (-3 elsewhere).  simulations/ground_truths.py:14-33 (the field),
+ * stream).  Same grids as ipp_generate_grf_rows (-3 elsewhere; ipp_set_grf_rows widens them).  simulations/ground_truths.py:14-33 (the field),
  * planning/mcts_zero/episode_generators.py:109-113 (a new episode's map, sampled when the previous one has run out of budget). */
 int ipp_generate_grf_refill(void* engine, int32_t n, const int32_t* refill /*[dev]*/, const int64_t* episode /*[dev] int64[capacity]*/,
                             int64_t row_offset, uint64_t seed, uint64_t subsequence, void* stream);

@@ -249,6 +249,8 @@ PROTOTYPES = {
     "ipp_mcts_backup": (C.c_int, [C.POINTER(IppMctsTables), C.c_int32, _P]),
     "ipp_mcts_policy": (C.c_int, [C.POINTER(IppMctsTables), _P, C.c_double, C.c_int32, _P, _P, _P, _P]),
     "ipp_tree_score_actions": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, C.c_uint32, _P, _P, _P]),
+    # (added without an ABI bump: no struct changes layout, every existing call answers as before until it is set)
+    "ipp_set_grf_rows": (C.c_int, [_P, C.c_int32]),
     "ipp_generate_grf": (C.c_int, [_P, C.c_int32, _P, _P, _P]),
     "ipp_generate_grf_rows": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_uint64, C.c_uint64, _P, _P]),
     "ipp_generate_grf_groups": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, C.c_int64, C.c_uint64, C.c_uint64, _P, _P]),

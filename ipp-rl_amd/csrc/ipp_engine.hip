@@ -78,6 +78,7 @@ struct Engine {
     bool grf_dft = false;  // even square grids up to 256: k_grf_dft instead of k_grf_conv + k_grf_norm
     int grf_tt = 0;        // > 0: even square grids up to 128: k_grf_hartley<grf_tt> (fp64 MFMA GEMMs)
     bool grf_fft = false;  // ... and n = 50 / 100: k_grf_fft (fast Hartley transforms) on the same amplitude table
+    bool grf_rows_all = false;  // ipp_set_grf_rows: every family above draws its own noise (rows / groups / refill calls on every even square grid <= 256)
     int grf_kc = 1;        // spectrum rows per LDS chunk
     int lut_cap;
     int lut_rows = 0;  // workgroup-per-item factor kernels: rows |drow| of the prior table kept in LDS
@@ -629,24 +630,29 @@ bool grf_hartley_tables_host(int n, int np, double c, std::vector<double>& hp, s
 // 8 waves (one owned 16-row tile each) from TT = 5: half the registers per wave of the 4-wave form, so that waves of the
 // streaming kernels still fit beside a field's workgroup on every SIMD
 template <int TT>
-void launch_grf_hartley(const View& v, int n, const float* white, const int32_t* env_ids, float* gt_out, hipStream_t s) {
+void launch_grf_hartley(const View& v, int n, const float* white, const int32_t* env_ids, float* gt_out, hipStream_t s, const GrfNoise& gn) {
     constexpr int NW = (TT > 4 && TT < 8) ? 8 : 4;  // (TT = 8 with one tile per wave spills 112 registers at the 168 it may use)
     // the grid sizes of BASELINE.json contract over ceil(n / 4) steps instead of the padded 4 TT (k_grf_hartley.h, KS)
     if (TT == 4 && v.W == 50)
         hipLaunchKernelGGL((k_grf_hartley<4, 4, 13>), dim3(n), dim3(256), grf_hartley_lds_bytes(4), s, v, env_ids, n, white,
-                           (const double*)v.grf_hp, (const double*)v.grf_amp, gt_out);
+                           (const double*)v.grf_hp, (const double*)v.grf_amp, gt_out, gn);
     else if (TT == 7 && v.W == 100)
         hipLaunchKernelGGL((k_grf_hartley<7, 8, 25>), dim3(n), dim3(512), grf_hartley_lds_bytes(7), s, v, env_ids, n, white,
-                           (const double*)v.grf_hp, (const double*)v.grf_amp, gt_out);
+                           (const double*)v.grf_hp, (const double*)v.grf_amp, gt_out, gn);
     else
         hipLaunchKernelGGL((k_grf_hartley<TT, NW>), dim3(n), dim3(64 * NW), grf_hartley_lds_bytes(TT), s, v, env_ids, n, white,
-                           (const double*)v.grf_hp, (const double*)v.grf_amp, gt_out);
+                           (const double*)v.grf_hp, (const double*)v.grf_amp, gt_out, gn);
 }
+
+// the engine's generator draws a field's white noise itself (GrfNoise): k_grf_fft always, the GEMM-Hartley and DFT families once
+// ipp_set_grf_rows has switched them on (grf_dft: every even square grid of 4 .. 256 cells a side)
+bool grf_draws_noise(const Engine* e) { return (e->grf_tt > 0 && e->grf_fft) || (e->grf_rows_all && e->grf_dft); }
 
 int launch_grf(Engine* e, int n, const float* white, float* raw, const int32_t* env_ids, float* gt_out, hipStream_t s,
                const GrfNoise* noise = nullptr) {
     const View& v = e->v;
-    if (!white && !(noise && e->grf_tt > 0 && e->grf_fft)) return fail(-1, "in-kernel ground-truth noise needs the fast Hartley path (50x50 / 100x100 grids)");
+    if (!white && !(noise && grf_draws_noise(e)))
+        return fail(-1, "in-kernel ground-truth noise needs the fast Hartley path (50x50 / 100x100 grids), or ipp_set_grf_rows(engine, 1) on an even square grid of 4 .. 256 cells a side");
     const GrfNoise gn = noise ? *noise : GrfNoise{nullptr, 0, 0, 0, 0, {0}, 0};
     if (v.W != v.H) return fail(-1, "device GRF needs a square grid (the reference transposes its dims, simulations/simulations.py:45-47)");
     if (e->grf_tt > 0 && e->grf_fft) {  // n = 50 / 100: fast Hartley transforms in LDS (k_grf_fft.h), same amplitude table
@@ -663,14 +669,14 @@ int launch_grf(Engine* e, int n, const float* white, float* raw, const int32_t* 
     }
     if (e->grf_tt > 0) {  // even n <= 128: four fp64 GEMMs on the matrix cores, normalisation fused (k_grf_hartley.h)
         switch (e->grf_tt) {
-            case 1: launch_grf_hartley<1>(v, n, white, env_ids, gt_out, s); break;
-            case 2: launch_grf_hartley<2>(v, n, white, env_ids, gt_out, s); break;
-            case 3: launch_grf_hartley<3>(v, n, white, env_ids, gt_out, s); break;
-            case 4: launch_grf_hartley<4>(v, n, white, env_ids, gt_out, s); break;
-            case 5: launch_grf_hartley<5>(v, n, white, env_ids, gt_out, s); break;
-            case 6: launch_grf_hartley<6>(v, n, white, env_ids, gt_out, s); break;
-            case 7: launch_grf_hartley<7>(v, n, white, env_ids, gt_out, s); break;
-            default: launch_grf_hartley<8>(v, n, white, env_ids, gt_out, s); break;
+            case 1: launch_grf_hartley<1>(v, n, white, env_ids, gt_out, s, gn); break;
+            case 2: launch_grf_hartley<2>(v, n, white, env_ids, gt_out, s, gn); break;
+            case 3: launch_grf_hartley<3>(v, n, white, env_ids, gt_out, s, gn); break;
+            case 4: launch_grf_hartley<4>(v, n, white, env_ids, gt_out, s, gn); break;
+            case 5: launch_grf_hartley<5>(v, n, white, env_ids, gt_out, s, gn); break;
+            case 6: launch_grf_hartley<6>(v, n, white, env_ids, gt_out, s, gn); break;
+            case 7: launch_grf_hartley<7>(v, n, white, env_ids, gt_out, s, gn); break;
+            default: launch_grf_hartley<8>(v, n, white, env_ids, gt_out, s, gn); break;
         }
         HIP_TRY(hipGetLastError());
         return 0;
@@ -683,7 +689,7 @@ int launch_grf(Engine* e, int n, const float* white, float* raw, const int32_t* 
         const int rows = (v.W + rgroups - 1) / rgroups;        // rows per thread
         const size_t lds = grf_dft_lds_bytes(v.W, e->grf_kc, small);
 #define IPP_GRF_LAUNCH(OPT, XB, NT, WLDS) \
-    hipLaunchKernelGGL((k_grf_dft<OPT, XB, NT, WLDS>), dim3(n), dim3(NT), lds, s, v, env_ids, n, white, v.grf_cs, v.grf_g, e->grf_kc, gt_out)
+    hipLaunchKernelGGL((k_grf_dft<OPT, XB, NT, WLDS>), dim3(n), dim3(NT), lds, s, v, env_ids, n, white, v.grf_cs, v.grf_g, e->grf_kc, gt_out, gn)
         if (small && xb == 4) IPP_GRF_LAUNCH(10, 4, 256, true);        // rows <= 10 for every n <= 100
         else if (small && rows <= 10) IPP_GRF_LAUNCH(10, 2, 256, true);
         else if (small) IPP_GRF_LAUNCH(20, 2, 256, true);              // n = 54 .. 98, n = 2 mod 4
@@ -1046,6 +1052,17 @@ int ipp_grf_generator(void* engine, int32_t* kind, int32_t* param) {  // (the or
     return 0;
 }
 
+int ipp_set_grf_rows(void* engine, int32_t all_grids) {
+    Engine* e = as_engine(engine);
+    if (!e) return fail(-1, "null engine");
+    if (all_grids != 0 && all_grids != 1) return fail(-1, "ipp_set_grf_rows: all_grids = %d, 0 or 1", all_grids);
+    if (all_grids && !e->grf_dft)
+        return fail(-1, "ipp_set_grf_rows: %d x %d (x_dim x y_dim) grid: generators that draw their own noise exist on even square grids of 4 .. 256 cells a side",
+                    e->v.W, e->v.H);
+    e->grf_rows_all = all_grids != 0;
+    return 0;
+}
+
 int ipp_engine_info(void* engine, ipp_info* out) {
     Engine* e = as_engine(engine);
     if (!e || !out) return fail(-1, "null argument");
@@ -1293,7 +1310,7 @@ int ipp_generate_grf_groups(void* engine, int32_t n, int32_t group_rows, const i
     if (n == 0) return 0;
     if (group_rows < 0 || (group_rows > 0 && (!group_subsequence || (n + group_rows - 1) / group_rows > 16)))
         return fail(-1, "ipp_generate_grf_groups: at most 16 groups of group_rows fields, with their subsequence offsets");
-    if (!(e->grf_tt > 0 && e->grf_fft)) return fail(-3, "ipp_generate_grf_rows: this grid has no generator that draws its own noise (ipp_fill_normal_rows + ipp_generate_grf)");
+    if (!grf_draws_noise(e)) return fail(-3, "ipp_generate_grf_rows: this grid has no generator that draws its own noise (ipp_fill_normal_rows + ipp_generate_grf; ipp_set_grf_rows)");
     HIP_TRY(hipSetDevice(e->device));
     GrfNoise gn = {row_ids, (long long)row_offset, seed, subsequence, group_rows, {0}, gt_out ? 0 : 1};
     for (int g = 0; group_rows > 0 && g < (n + group_rows - 1) / group_rows; ++g) gn.group_subseq[g] = (long long)group_subsequence[g];
@@ -1307,7 +1324,7 @@ int ipp_generate_grf_refill(void* engine, int32_t n, const int32_t* refill, cons
     if (!refill || !episode) return fail(-1, "ipp_generate_grf_refill: refill and episode are required");
     if (n < 0 || n > e->v.max_batch) return fail(-1, "n = %d outside [0, max_batch = %d]", n, e->v.max_batch);
     if (n == 0) return 0;
-    if (!(e->grf_tt > 0 && e->grf_fft)) return fail(-3, "ipp_generate_grf_refill: this grid has no generator that draws its own noise (50x50 / 100x100 grids)");
+    if (!grf_draws_noise(e)) return fail(-3, "ipp_generate_grf_refill: this grid has no generator that draws its own noise (50x50 / 100x100 grids; ipp_set_grf_rows)");
     HIP_TRY(hipSetDevice(e->device));
     GrfNoise gn = {refill, (long long)row_offset, seed, subsequence, 0, {0}, 1, reinterpret_cast<const long long*>(episode)};
     return launch_grf(e, n, nullptr, e->v.grf_raw2, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream), &gn);

@@ -17,6 +17,7 @@
 // (workgroup min / max), the field goes straight to the env slot or the caller's buffer.
 #pragma once
 #include "ipp_common.h"
+#include "k_grf_noise.h"
 
 namespace ipp {
 
@@ -30,7 +31,7 @@ __host__ __device__ inline size_t grf_dft_lds_bytes(int n, int kc, bool w_in_lds
 //   stage 1: A[k][x] = sum_y w[y][x] (cos - i sin)(2 pi k y / n)
 //   stage 2: D[k][x] = sum_x' A[k][x'] g_k[(x - x') mod n]
 template <int XB, int NT>
-__device__ __forceinline__ void grf_stage12(const int n, const int k0, const int kn, const float* __restrict__ wsrc,
+__device__ __forceinline__ void grf_stage12(const int n, const int k0, const int kn, const float* wsrc,
                                             const double2* __restrict__ cs_s, const double* __restrict__ gs,
                                             double2* __restrict__ A, double2* __restrict__ D, const int tid) {
     typedef float wvec __attribute__((ext_vector_type(XB)));
@@ -97,16 +98,22 @@ __device__ __forceinline__ void grf_stage12(const int n, const int k0, const int
 // (R = NT / (n / XB3) row groups, at most OPT rows per thread: OPT >= ceil(n / R)), all of them in registers across
 // the chunks of the spectrum: per k a thread reads XB3 spectrum values and one twiddle per row for 2 XB3 FMAs each.
 // NT: workgroup size; WLDS: white noise staged in LDS.  XB3 divides n.
+// white == nullptr: the field's white noise is drawn in the kernel (GrfNoise, k_grf_noise.h) -- WLDS: into the LDS copy instead of
+// loading it; else (it does not fit LDS beside the tables and every spectrum chunk reads it again) into the field's OWN DESTINATION,
+// 16-byte vector stores published by a workgroup barrier, read from there in stage 1 and overwritten by the normalised field only
+// behind the barrier that ends the last chunk's grf_stage12.  So `white` and `gt_out` may name the same memory: no __restrict__ on
+// them.  The field may go to the env's alternate plane (gn.to_alt); with a caller's white noise gn is all zeros.
 template <int OPT, int XB3, int NT, bool WLDS>
 __global__ __launch_bounds__(NT) void k_grf_dft(View v, const int* __restrict__ env_ids, int n_items,
-                                                         const float* __restrict__ white, const double2* __restrict__ cs,
+                                                         const float* white, const double2* __restrict__ cs,
                                                          const double* __restrict__ g, int kc,
-                                                         float* __restrict__ gt_out) {
+                                                         float* gt_out, GrfNoise gn) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_dft[];
     const int n = v.W, N = v.N;
     const int item = blockIdx.x;
     if (item >= n_items) return;
-    const int env = gt_out ? 0 : (env_ids ? env_ids[item] : item);
+    if (grf_noise_skip(white, gn, item)) return;  // (padding row of a staged block, no reset at this position)
+    const int env = grf_item_env(gt_out, env_ids, gn, item);
     if (env < 0 || env >= v.cap) return;
     double2* cs_s = reinterpret_cast<double2*>(smem_dft);
     double2* A = cs_s + n;
@@ -116,10 +123,17 @@ __global__ __launch_bounds__(NT) void k_grf_dft(View v, const int* __restrict__ 
     float* ws = reinterpret_cast<float*>(gs + (size_t)kc * n);
     double* red = reinterpret_cast<double*>(ws + (WLDS ? N : 0));  // [2 * waves] min / max per wave (N is even)
     const int tid = threadIdx.x;
-    const float* __restrict__ wn = white + (size_t)item * N;
-    if (WLDS)
-        for (int i = tid; i < N; i += kGrfThreads) ws[i] = wn[i];
-    const float* __restrict__ wsrc = WLDS ? ws : wn;
+    float* gt = grf_dest(v, gt_out, gn, item, env, N);
+    const float* wn = white ? white + (size_t)item * N : gt;
+    if (WLDS) {
+        if (white)
+            for (int i = tid; i < N; i += kGrfThreads) ws[i] = wn[i];
+        else
+            grf_noise_draw<NT>(gn, item, env, gn.episode != nullptr, N, tid, [&](int e, float x) { ws[e] = x; });
+    } else if (!white) {
+        grf_noise_store<NT>(gn, item, env, gn.episode != nullptr, N, tid, gt);  // (visible to the workgroup behind the first chunk's barrier)
+    }
+    const float* wsrc = WLDS ? ws : wn;
     for (int i = tid; i < n; i += kGrfThreads) cs_s[i] = cs[i];
 
     const int ncg = n / XB3;
@@ -189,7 +203,6 @@ __global__ __launch_bounds__(NT) void k_grf_dft(View v, const int* __restrict__ 
     for (int w = 1; w < NW; ++w) { dlo = fmin(dlo, red[w]); dhi = fmax(dhi, red[NW + w]); }
     const double span = dhi - dlo;
     typedef float outv __attribute__((ext_vector_type(XB3)));
-    float* gt = gt_out ? gt_out + (size_t)item * N : gt_plane(v, env);
     if (own) {
 #pragma unroll
         for (int j = 0; j < OPT; ++j) {
@@ -202,8 +215,7 @@ __global__ __launch_bounds__(NT) void k_grf_dft(View v, const int* __restrict__ 
             }
         }
     }
-    if (!gt_out)
-        for (int i = N + tid; i < v.Npad; i += kGrfThreads) gt[i] = 0.f;
+    grf_dest_finish<NT>(v, gt_out, gn, gt, env, N, tid);
 }
 
 }  // namespace ipp

@@ -18,6 +18,7 @@
 #pragma once
 #include "ipp_common.h"
 #include "k_misc.h"
+#include "k_grf_noise.h"
 
 namespace ipp {
 
@@ -126,20 +127,8 @@ __device__ __forceinline__ void grf_fft_pass(T* X, int sv, int sj, const double2
     __syncthreads();
 }
 
-// Where the white noise of a field comes from when it is drawn in the kernel (white == nullptr): the numbers ipp_fill_normal_rows would
-// have written for row id (row_ids ? row_ids[item] : item) + row_offset of a row_len = N fill -- the fill kernel's 4 N bytes per field
-// written and read back (160 MB per step of configs[2], 13 % of its GPU time) do not exist then.
-struct GrfNoise {
-    const int* row_ids;
-    long long row_offset;
-    uint64_t seed, subseq;
-    // fields of several episodes in one launch (ipp_generate_grf_groups): field i belongs to group i / group_rows and draws from
-    // subseq + group_subseq[group] (by value: no upload in front of the launch); group_rows == 0: one group.  A NEGATIVE row id skips the field.
-    int group_rows;
-    long long group_subseq[16];
-    int to_alt;  // gt_out == NULL: field i goes to the ALTERNATE ground-truth plane of env row_ids[i] (staged for its next episode; the reset flips)
-    const long long* episode;  // REFILL (ipp_generate_grf_refill): [capacity] current episode of every env; field i draws from subseq + episode[env] + 1
-};
+// (GrfNoise -- where the white noise of a field comes from when it is drawn in the kernel, white == nullptr -- and the destinations:
+// k_grf_noise.h, shared with the other generator families)
 
 // One workgroup per field.  white [n_items][N] float standard normals (or nullptr: GrfNoise); amp [n][amp_ld] doubles (the table of
 // k_grf_hartley.h: zero padded, leading dimension amp_ld); result into the env slots (gt_out == nullptr) or gt_out [n_items][N].
@@ -156,8 +145,8 @@ __global__ __launch_bounds__(N1 == 10 ? 512 : 256) void k_grf_fft(View v, const 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_gf[];
     const int item = blockIdx.x;
     if (item >= n_items) return;
-    if (!white && gn.row_ids && gn.row_ids[item] < 0) return;  // (padding row of a staged block)
-    const int env = gt_out ? 0 : (gn.to_alt ? gn.row_ids[item] : (env_ids ? env_ids[item] : item));
+    if (grf_noise_skip(white, gn, item)) return;  // (padding row of a staged block)
+    const int env = grf_item_env(gt_out, env_ids, gn, item);
     if (env < 0 || env >= v.cap) return;
     T* X = reinterpret_cast<T*>(smem_gf);
     // min / max per wave: behind the array (n = 50) or, at n = 100 where the array fills the workgroup's 80 KB, in its first row once the
@@ -175,19 +164,7 @@ __global__ __launch_bounds__(N1 == 10 ? 512 : 256) void k_grf_fft(View v, const 
                 X[y * LD + x + 1] = (T)wv.y;
             }
         } else {
-            const uint64_t rid = (uint64_t)((gn.row_ids ? (long long)gn.row_ids[item] : (long long)item) + gn.row_offset);
-            const uint64_t subseq = REFILL ? gn.subseq + (uint64_t)(gn.episode[env] + 1)
-                                           : gn.subseq + (gn.group_rows > 0 ? (uint64_t)gn.group_subseq[min(item / gn.group_rows, 15)] : 0ull);
-            constexpr int qpr = (N + 3) / 4;  // counters per row: element e of the row is normal e & 3 of counter rid * qpr + (e >> 2)
-            for (int qc = tid; qc < qpr; qc += NT) {
-                float nrm[4];
-                philox_normal4(rid * (uint64_t)qpr + (uint64_t)qc, subseq, gn.seed, nrm);
-#pragma unroll
-                for (int h = 0; h < 4; ++h) {
-                    const int e = 4 * qc + h;
-                    if (e < N) { const int y = e / n; X[y * LD + (e - y * n)] = (T)nrm[h]; }
-                }
-            }
+            grf_noise_draw<NT>(gn, item, env, REFILL, N, tid, [&](int e, float x) { const int y = e / n; X[y * LD + (e - y * n)] = (T)x; });
         }
     }
     __syncthreads();
@@ -221,15 +198,13 @@ __global__ __launch_bounds__(N1 == 10 ? 512 : 256) void k_grf_fft(View v, const 
     // (x - lo) * (1 / span) in fp64, rounded to fp32: the quotient's fp32 rounding except where the fp64 value sits within an fp64 ulp
     // of an fp32 rounding boundary (1 cell in 10^8); 10^4 fp64 divisions per field were a third of the kernel's time
     const double inv_span = 1.0 / (dhi - dlo);
-    float* gt = gt_out ? gt_out + (size_t)item * N : (gn.to_alt ? v.gt + (size_t)gt_alt_slot(v, env) * v.Npad : gt_plane(v, env));
+    float* gt = grf_dest(v, gt_out, gn, item, env, N);
 #pragma unroll
     for (int q = 0; q < PER; ++q) {
         const int i = tid + q * NT;
         if (i < N) gt[i] = (float)(((double)val[q] - dlo) * inv_span);
     }
-    if (!gt_out)
-        for (int i = N + tid; i < v.Npad; i += NT) gt[i] = 0.f;
-    if (!gt_out && gn.to_alt && tid == 0) v.gt_slot[v.cap + env] = 1;  // the env's next folded reset may flip (stream order: the reset's launch waits for this one)
+    grf_dest_finish<NT>(v, gt_out, gn, gt, env, N, tid);
 }
 
 }  // namespace ipp

@@ -23,6 +23,7 @@
 // C/D[row = (lane >> 4) + 4 reg][col = lane & 15], 4 f64 per lane.
 #pragma once
 #include "ipp_common.h"
+#include "k_grf_noise.h"
 
 namespace ipp {
 
@@ -81,32 +82,38 @@ __device__ __forceinline__ void grf_store_t(double* X, int ld, int wave, int lan
     }
 }
 
+// white == nullptr: the field's white noise is drawn straight into X (GrfNoise, k_grf_noise.h) instead of loaded -- it is staged in
+// LDS either way -- and the field may go to the env's alternate plane (gn.to_alt); with a caller's white noise gn is all zeros.
 template <int TT, int NW, int KS = 4 * TT>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8 ? 3 : 1))) void k_grf_hartley(View v, const int* __restrict__ env_ids, int n_items,
                                                      const float* __restrict__ white, const double* __restrict__ Hp,
-                                                     const double* __restrict__ ampp, float* __restrict__ gt_out) {
+                                                     const double* __restrict__ ampp, float* __restrict__ gt_out, GrfNoise gn) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_gh[];
     constexpr int NP = 16 * TT, LD = NP + 1, NT = 64 * NW, OW = (TT + NW - 1) / NW;
     static_assert(OW <= 2, "at most two owned tiles per wave");
     const int n = v.W, N = v.N;
     const int item = blockIdx.x;
     if (item >= n_items) return;
-    const int env = gt_out ? 0 : (env_ids ? env_ids[item] : item);
+    if (grf_noise_skip(white, gn, item)) return;  // (padding row of a staged block, no reset at this position)
+    const int env = grf_item_env(gt_out, env_ids, gn, item);
     if (env < 0 || env >= v.cap) return;
     double* X = reinterpret_cast<double*>(smem_gh);
     double* red = X + (size_t)NP * LD;  // [2][8] min / max per wave
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const float* __restrict__ wn = white + (size_t)item * N;
     // white noise -> fp64 in LDS: pairs of cells (n is even, so a pair never straddles a row), zero padding to NP x NP
     {
-        const float2* __restrict__ w2 = reinterpret_cast<const float2*>(wn);
-        const int half = n / 2, n2 = n * half;
+        if (white) {
+            const float2* __restrict__ w2 = reinterpret_cast<const float2*>(white + (size_t)item * N);
+            const int half = n / 2, n2 = n * half;
 #pragma unroll 4
-        for (int i = tid; i < n2; i += NT) {
-            const float2 wv = w2[i];
-            const int y = i / half, x = 2 * (i - y * half);
-            X[y * LD + x] = (double)wv.x;
-            X[y * LD + x + 1] = (double)wv.y;
+            for (int i = tid; i < n2; i += NT) {
+                const float2 wv = w2[i];
+                const int y = i / half, x = 2 * (i - y * half);
+                X[y * LD + x] = (double)wv.x;
+                X[y * LD + x + 1] = (double)wv.y;
+            }
+        } else {
+            grf_noise_draw<NT>(gn, item, env, gn.episode != nullptr, N, tid, [&](int e, float x) { const int y = e / n; X[y * LD + (e - y * n)] = (double)x; });
         }
         const int padc = NP - n;  // columns n .. NP-1 of the rows < n, then whole rows n .. NP-1
         for (int i = tid; i < n * padc; i += NT) X[(i / padc) * LD + n + i % padc] = 0.0;
@@ -163,7 +170,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
 #pragma unroll
     for (int w = 1; w < NW; ++w) { dlo = fmin(dlo, red[w]); dhi = fmax(dhi, red[8 + w]); }
     const double span = dhi - dlo;
-    float* gt = gt_out ? gt_out + (size_t)item * N : gt_plane(v, env);
+    float* gt = grf_dest(v, gt_out, gn, item, env, N);
 #pragma unroll
     for (int o = 0; o < OW; ++o) {
         if (wave + NW * o >= TT) break;
@@ -175,8 +182,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
                 if (row < n && col < n) gt[col * n + row] = (float)((acc[o][t][r] - dlo) / span);  // (acc holds field^T)
             }
     }
-    if (!gt_out)
-        for (int i = N + tid; i < v.Npad; i += NT) gt[i] = 0.f;
+    grf_dest_finish<NT>(v, gt_out, gn, gt, env, N, tid);
 }
 
 }  // namespace ipp

@@ -226,19 +226,39 @@ class DeviceArena:
             pass
 
 
+GRF_ROWS_MAX = 256  # largest grid side of the generators that draw their own noise (ipp_set_grf_rows)
+
+
+def check_grf_rows(grf_rows):
+    """grf_rows of IPPEngine / VecIPPEnv: None or "all"; anything else raises ValueError (before any device call)."""
+    if grf_rows is not None and not (isinstance(grf_rows, str) and grf_rows == "all"):
+        raise ValueError(f"grf_rows = {grf_rows!r}: None (50x50 / 100x100 grids only) or 'all' (every even square grid up to {GRF_ROWS_MAX})")
+    return grf_rows
+
+
+def grf_rows_grid_ok(x_dim: int, y_dim: int) -> bool:
+    """The grid rule of grf_rows="all" (ipp_set_grf_rows): square, even, 4 .. 256 cells a side -- where the reference's spectral
+    amplitude is even in each index (simulations/ground_truths.py:7-11) and a field fits one workgroup's generator."""
+    return x_dim == y_dim and x_dim % 2 == 0 and 4 <= x_dim <= GRF_ROWS_MAX
+
+
 class IPPEngine:
     """B environment slots on one GPU; state lives in one caller-owned arena tensor."""
 
     def __init__(self, cfg: EngineConfig, capacity: int, state: str = "factor", rank_cap: int = 360,
                  max_batch: Optional[int] = None, device: str = "cuda:0", max_measurements: int = 9,
                  tile_threads: int = 0, window_rows: int = 0, score_scratch: bool = False, node_capacity: int = 0,
-                 fixed_prior: bool = False, arena=None):
+                 fixed_prior: bool = False, arena=None, grf_rows: Optional[str] = None):
         """arena: None / "auto" = a torch.uint8 tensor for small arenas, a "vmm" DeviceArena from 256 MiB; "torch"; "hip" / "vmm" = a
         DeviceArena of that kind owned by the engine; a DeviceArena instance = the caller's (the engine never frees it).
         window_rows: 0 = exact columns, R > 0 = columns kept within R grid rows of their footprint, -1 = the smallest
         R the engine accepts for this prior (ipp_min_window_rows).  fixed_prior: no reset will install a length scale above
         cfg.length_scale (no shuffle_prior_cov), which lets the window be 10 instead of 12 rows for the example config.
-        The prior is sigma^2 * Matern(l, cfg.nu) for nu in 0.5, 1.5, 2.5, inf (prior_kernel); other nu raise ValueError."""
+        The prior is sigma^2 * Matern(l, cfg.nu) for nu in 0.5, 1.5, 2.5, inf (prior_kernel); other nu raise ValueError.
+        grf_rows: None = generate_grf_rows / generate_fields_rows / generate_fields_refill draw a GRF's white noise in the generator
+        on 50x50 and 100x100 grids only (False elsewhere); "all" = on every even square grid of 4 .. 256 cells a side
+        (ipp_set_grf_rows; a grid outside that rule raises ValueError and builds nothing)."""
+        self._grf_rows = check_grf_rows(grf_rows)
         if _forked_with_gpu:
             raise _ffi.IppError(FORK_MESSAGE)
         torch = _torch()
@@ -335,6 +355,16 @@ class IPPEngine:
         self.info = info
         self.n_cells, self.n_pad, self.meas_cap = info.n_cells, info.n_pad, info.meas_cap
         self.rank_cap = int(rank_cap)
+        if self._grf_rows == "all":
+            if self._lib.ipp_set_grf_rows(self._h, 1) != 0:
+                msg = self._lib.ipp_last_error().decode(errors="replace")
+                self.close()
+                raise ValueError(f"grf_rows='all': {msg}")
+
+    @property
+    def grf_rows(self) -> Optional[str]:
+        """None or "all": which grids the generators that draw their own noise serve (read-only; set at construction)."""
+        return self._grf_rows
 
     @property
     def prior_kernel(self) -> str:

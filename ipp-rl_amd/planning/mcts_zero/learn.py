@@ -125,7 +125,7 @@ class Learner:
         self.reported: Dict[int, int] = {}  # iteration -> rows its self-play reported (for `evicted`)
         self.history: List[Dict] = []
         kw = dict(selfplay_kwargs)
-        self._arena_kwargs = {k: kw[k] for k in ("sims_in_flight", "tie_break", "groups", "device") if k in kw}
+        self._arena_kwargs = {k: kw[k] for k in ("sims_in_flight", "tie_break", "groups", "device", "grf_rows") if k in kw}
         W = int(kw.get("sims_in_flight", 4))
         device = kw.get("device", "cuda:0")
         if net_max_batch is None:

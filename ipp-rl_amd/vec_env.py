@@ -26,7 +26,7 @@ from contextlib import nullcontext as _nullcontext
 import numpy as np
 
 from . import _ffi
-from .engine import EngineConfig, IPPEngine
+from .engine import EngineConfig, IPPEngine, check_grf_rows
 from .fields import check_hotspot, field_kind
 
 INIT_ACTION = (2.0, 2.0, 14.0)  # planning/missions.py:69
@@ -164,7 +164,7 @@ class VecIPPEnv:
                  rank_cap: Optional[int] = None, stagger: bool = False, tile_threads: int = 0,
                  adaptive: bool = True, use_flight_time: bool = True, window_rows: int = 0, fused_reset: bool = True,
                  parts: int = 1, arena=None, budget: Optional[float] = None, shuffle_budget: bool = False, feature_history: int = 0,
-                 node_capacity: int = 0, max_batch: Optional[int] = None, spare_slots: int = 0):
+                 node_capacity: int = 0, max_batch: Optional[int] = None, spare_slots: int = 0, grf_rows: Optional[str] = None):
         """budget=None: episodes of exactly `episode_steps` steps on a schedule known to the host.  budget=B0: the reference's
         budget-driven episodes (planning/mcts_zero/episode_generators.py:109-150) -- `episode_steps` is max_episode_steps, every env
         carries a device-side ledger (self.budget, self.depth, self.episode, self.done) that the step kernel charges with the action
@@ -176,7 +176,11 @@ class VecIPPEnv:
         head-room (fixed_prior=False).  node_capacity / max_batch: the engine's tree nodes and largest launch
         (IPPEngine), for a search whose roots are the env slots (planning/mcts_zero/selfplay.py); the defaults build no nodes and launches of
         num_envs items.  spare_slots=K: the engine gets num_envs + K slots; [0, num_envs) are the envs, the slots above them are never
-        stepped or reset by the env (the compact replay ring archives ended episodes there); K = 0 builds exactly the engine without it."""
+        stepped or reset by the env (the compact replay ring archives ended episodes there); K = 0 builds exactly the engine without it.
+        grf_rows: None = Gaussian random fields whose generator draws its own noise on 50x50 / 100x100 grids only (budget mode: those
+        two grids); "all" = on every even square grid of 4 .. 256 cells a side (IPPEngine(grf_rows=...)): budget mode then runs GRF
+        episodes on every such grid with the patch layout, and the scheduled mode stages its blocks through the rows call."""
+        check_grf_rows(grf_rows)
         import torch
 
         self.torch = torch
@@ -212,8 +216,9 @@ class VecIPPEnv:
                                  "device's Philox streams (vec_env.start_prior: the same distribution, other values)")
             if state != "factor":
                 raise ValueError("budget mode: patch-layout factor engines only (state='factor')")
-            if self.field_kind == _ffi.IPP_FIELD_GRF and (cfg.x_dim != cfg.y_dim or cfg.x_dim not in (50, 100)):
-                raise ValueError("budget mode: grids whose ground-truth generator draws its own noise only (50x50, 100x100)")
+            if self.field_kind == _ffi.IPP_FIELD_GRF and grf_rows is None and (cfg.x_dim != cfg.y_dim or cfg.x_dim not in (50, 100)):
+                raise ValueError("budget mode: grids whose ground-truth generator draws its own noise only (50x50, 100x100; "
+                                 "grf_rows='all': every even square grid up to 256)")
             if not (self.initial_budget >= cfg.resolution):
                 raise ValueError(f"budget mode: budget {budget} below the grid resolution {cfg.resolution}")
             if shuffle_budget and not (self.initial_budget >= 10.0):
@@ -225,7 +230,7 @@ class VecIPPEnv:
         self.engine = IPPEngine(cfg, capacity=self.num_envs + self.spare_slots, state=state, rank_cap=rank_cap, device=device,
                                 tile_threads=tile_threads, window_rows=window_rows, fixed_prior=not shuffle_prior_cov,
                                 arena=arena, node_capacity=int(node_capacity),
-                                max_batch=max_batch if (max_batch or not self.spare_slots) else self.num_envs)
+                                max_batch=max_batch if (max_batch or not self.spare_slots) else self.num_envs, grf_rows=grf_rows)
         if self.budget_mode and (int(self.engine.info.patch_layout) != 1 or int(self.engine.info.fused_step) != 1):
             self.engine.close()
             raise ValueError("budget mode: patch-layout engines only (windowed factor state, ipp_info.patch_layout == 1)")

@@ -91,13 +91,16 @@ def main():
     ap.add_argument("--planes", choices=["dense", "compact"], default="dense", help="the ring: dense planes or compact rows")
     ap.add_argument("--shuffle-prior", action="store_true",
                     help="shuffle_prior_cov: every self-play episode draws its own prior on the device (Learner(episode_priors='device'))")
+    ap.add_argument("--simulation", default="split_random_field",
+                    help="ground-truth kind (sensor.simulation.type); gaussian_random_field runs the 40x40 grid with grf_rows='all'")
     a = ap.parse_args()
     import torch
 
     from ipp_rl_amd import EngineConfig
     from ipp_rl_amd.planning.mcts_zero import Learner, PolicyValueNetwork
 
-    cfg = EngineConfig(x_dim=40, y_dim=40, simulation="split_random_field")
+    cfg = EngineConfig(x_dim=40, y_dim=40, simulation=a.simulation)
+    grf = dict(grf_rows="all") if a.simulation == "gaussian_random_field" else {}
     hp, md = params(a.sims)
     net_hp = dict(input_channels=6, num_channels=8, dropout=0.0, use_silu=True, num_encoder_res_blocks=a.blocks, use_separable_conv_layers=True,
                   use_global_context_mixing=True, num_global_pooling_channels=4, num_policy_head_conv_bn_blocks=1, num_value_head_conv_bn_blocks=1,
@@ -118,13 +121,13 @@ def main():
     with tempfile.TemporaryDirectory() as tmp:
         t0 = time.perf_counter()
         lr = Learner(cfg, a.envs, hp, md, module, tmp, episodes_per_env=a.episodes, capacity=a.envs * slots, sims_in_flight=2,
-                     planes=True if a.planes == "dense" else "compact", episode_priors="device" if a.shuffle_prior else None)
+                     planes=True if a.planes == "dense" else "compact", episode_priors="device" if a.shuffle_prior else None, **grf)
         build = time.perf_counter() - t0
         recs = lr.learn()
         sp = lr.selfplay
         cost = commit_cost(sp, a.steps)
         ring = ring_cost(sp, int(hp["batch_size"]))
-        out = dict(ring=ring, shuffle_prior=bool(a.shuffle_prior), envs=a.envs, sims=a.sims, blocks=a.blocks, episodes_per_env=a.episodes, ring_rows=a.envs * slots,
+        out = dict(ring=ring, simulation=a.simulation, shuffle_prior=bool(a.shuffle_prior), envs=a.envs, sims=a.sims, blocks=a.blocks, episodes_per_env=a.episodes, ring_rows=a.envs * slots,
                    ring_plane_gib=round(a.envs * slots * 6 * cfg.n_cells ** 2 * 4 / 2 ** 30, 2) if a.planes == "dense" else 0.0, build_s=round(build, 2),
                    iterations=[dict(iteration=r["iteration"], steps=r["totals"]["steps"], examples=r["totals"]["examples"],
                                     window_length=r["window_length"], evicted=r["evicted"],

@@ -6,7 +6,7 @@ and a prioritised-replay leg on the big ring: the PER minibatch (ipp_replay_mass
 against the uniform minibatch (the committed prefix count + ipp_replay_gather) at the same n, alternating.
 
     python tools/selfplay_bench.py [--envs 4096] [--dim 50] [--sims 100] [--steps 8] [--warmup 2] [--planes-envs 8]
-                                   [--per-batch 1024] [--per-reps 20] [--planes {dense,compact}]
+                                   [--per-batch 1024] [--per-reps 20] [--planes {dense,compact}] [--simulation KIND]
 
 The 4096-env run keeps no planes (a 50x50 plane is 25 MB per channel): its planes phase is reported as not measured; the planes phase
 and the gather kernel (CUDA events around the ipp_replay_gather launch alone, one minibatch of --batch rows with one augmented copy) are
@@ -140,16 +140,21 @@ def main():
                     help="shuffle_prior_cov: every episode draws its own prior on the device (SelfPlay(episode_priors='device'))")
     ap.add_argument("--window-rows", type=int, default=-1,
                     help="column window of the envs' engines (-1: the smallest the prior allows; 12 = the shuffled priors' window without them)")
+    ap.add_argument("--simulation", default=None,
+                    help="ground-truth kind (sensor.simulation.type): gaussian_random_field, hotspot_random_field or split_random_field; "
+                         "default: EngineConfig's.  A Gaussian random field on a grid other than 50 / 100 runs with grf_rows='all'")
     a = ap.parse_args()
     import torch
 
     from ipp_rl_amd import EngineConfig
     from ipp_rl_amd.planning.mcts_zero import SelfPlay
 
-    cfg = EngineConfig(x_dim=a.dim, y_dim=a.dim)
+    cfg = EngineConfig(x_dim=a.dim, y_dim=a.dim) if a.simulation is None else EngineConfig(x_dim=a.dim, y_dim=a.dim, simulation=a.simulation)
     hp, md = params(a.sims, a.episode_steps)
     hp["shuffle_prior_cov"] = bool(a.shuffle_prior)
     kw = dict(episode_priors="device" if a.shuffle_prior else None, window_rows=a.window_rows)
+    if cfg.simulation == "gaussian_random_field" and a.dim not in (50, 100):
+        kw["grf_rows"] = "all"
     sp = SelfPlay(cfg, a.envs, hp, md, planes=False, seed=1, **kw)
     sp.run(a.warmup)
     wall, split = timed(sp, a.steps)
@@ -175,7 +180,7 @@ def main():
     ring = ring_leg(small, a.batch)
     small.close()
     split["planes"] = "not measured: the 4096-env batch keeps no planes (planes=False); see planes_ms_small_batch"
-    out = {"envs": a.envs, "grid": a.dim, "sims": a.sims, "steps": a.steps, "shuffle_prior": bool(a.shuffle_prior), "window_rows": window_rows,
+    out = {"envs": a.envs, "grid": a.dim, "simulation": cfg.simulation, "grf_rows": kw.get("grf_rows"), "sims": a.sims, "steps": a.steps, "shuffle_prior": bool(a.shuffle_prior), "window_rows": window_rows,
            "samples_per_s": a.envs * a.steps / wall,
            "step_ms": 1e3 * wall / a.steps, "split_ms": split, "episodes_ended_last_step": ended,
            "roots_with_policy_last_step": with_policy, "gather_kernel_ms_small_batch": gather_ms, "gathered_rows": gathered_rows,
